@@ -12,7 +12,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 out=gpurun_out/prof/$tag
 mkdir -p "$out"
-args="--steps 10 --warmup 3 --cpu-budget 0 $*"
+args="--full --steps 10 --warmup 3 --cpu-budget 0 $*"
 echo "[profile] trace: bench.py $args"
 timeout -k 10 300 rocprofv3 --kernel-trace --marker-trace --stats -d "$out/trace" -o run -f csv -- \
     python3 bench.py $args > "$out/bench_trace.json" 2> "$out/bench_trace.err" || { echo "trace pass failed"; tail -20 "$out/bench_trace.err"; exit 1; }

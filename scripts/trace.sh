@@ -9,6 +9,6 @@ export TMPDIR=/tmp
 out=gpurun_out/prof/$tag
 mkdir -p "$out"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/trace" -o run -f csv -- \
-    python3 bench.py --steps 10 --warmup 3 --cpu-budget 0 "$@" > "$out/bench_trace.json" 2> "$out/bench_trace.err" \
+    python3 bench.py --full --steps 10 --warmup 3 --cpu-budget 0 "$@" > "$out/bench_trace.json" 2> "$out/bench_trace.err" \
     || { echo "trace failed"; tail -20 "$out/bench_trace.err"; exit 1; }
 ls "$out/trace"
