@@ -405,6 +405,61 @@ int32_t ngx_synchronize(ngx_ctx* ctx);
  * Call it before any other call on the context (the result arrays are valid until then). */
 int32_t ngx_go_result_digest(ngx_ctx* ctx, const ngx_go_result* r, uint64_t out[3]);
 
+/* ---------------------------------------------------------------- GROUP BY over a GO result */
+/* `GO ... | GROUP BY <keys> YIELD <aggregates>` with the grouping on the device: replaces
+ * GroupByExecutor::groupingData (src/graph/GroupByExecutor.cpp:236-331; the functions of
+ * src/graph/AggregateFunction.h) for a result that stayed in HBM. Only the group rows cross PCIe.
+ * `r` is a result_on_device result of this context, and the call comes before any other call on the
+ * context (as ngx_go_result_digest). Columns are named by their GO YIELD index.
+ *   keys     1 to 4 columns of static type INT / VID / TIMESTAMP / BOOL / STRING
+ *   values   static type INT / VID / TIMESTAMP / DOUBLE (AVG: INT / DOUBLE), or an integer / double
+ *            constant (col -1, konst), under every function but STD; COUNT and COUNT_DISTINCT take any
+ *            static type and `*` (col -1, a string konst)
+ * NGX_E_UNSUPPORTED, with the reason in ngx_last_error, for: DOUBLE keys, UNKNOWN-typed (per-row type)
+ * columns, STD, more than 4 keys, more than 64 yields, a bare yield column that is not a key, world > 1
+ * (the shards' partial states are not merged yet). The caller then groups on the host.
+ * Results follow the reference per function: integer results exactly (sums wrap in two's complement; VID
+ * and TIMESTAMP sums keep their type; BIT_* of a non-INT column is 0); double SUM / AVG depend on the
+ * order the rows arrive in, as the reference's do on the order of the storage responses, and are not
+ * bit-reproducible. Output types are those of the result cells; the order of the group rows is not fixed.
+ * Flags: "group_by_device" counts the calls completed on the device, "group_by_lds" those whose
+ * accumulation ran per workgroup in LDS; "group_lds_max" (-1: by size) is the largest number of groups
+ * that takes the LDS path, 0 forces global atomics. */
+#define NGX_AGG_GROUP 0                /* no function: a key column or a constant */
+#define NGX_AGG_COUNT 1
+#define NGX_AGG_COUNT_DISTINCT 2
+#define NGX_AGG_SUM 3
+#define NGX_AGG_AVG 4
+#define NGX_AGG_MAX 5
+#define NGX_AGG_MIN 6
+#define NGX_AGG_STD 7
+#define NGX_AGG_BIT_AND 8
+#define NGX_AGG_BIT_OR 9
+#define NGX_AGG_BIT_XOR 10
+typedef struct {
+    int32_t fn;                        /* NGX_AGG_* */
+    int32_t col;                       /* GO YIELD column, -1: `*' / constant */
+    ngx_cell konst;                    /* col == -1: the constant (a string constant carries no bytes) */
+} ngx_agg_col;
+typedef struct {
+    int32_t nkeys;
+    const int32_t* key_cols;
+    int32_t nyields;
+    const ngx_agg_col* yields;
+} ngx_group_plan;
+typedef struct {
+    int32_t code;
+    int32_t ncols;                     /* the plan's nyields */
+    const int32_t* col_types;          /* NGX_T_* of the first group row's cells (0 when there are no groups) */
+    uint64_t ngroups;
+    const ngx_cell* cells;             /* cells[group * ncols + col] */
+    const char* strings;
+    uint64_t strings_len;
+    double device_ms;                  /* HIP-event time of the grouping, table clear to the last cell */
+} ngx_group_result;
+int32_t ngx_go_group_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_group_plan* plan, ngx_group_result** out);
+void ngx_group_result_free(ngx_group_result* r);
+
 /* ---------------------------------------------------------------- measurement hooks */
 /* Per-kernel device times of the last ngx_go (HIP events on the engine stream), for bench.py. */
 typedef struct {

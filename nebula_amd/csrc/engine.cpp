@@ -230,6 +230,12 @@ struct ngx_ctx {
     DBuf pwF, pwIn, pwEst, pwCf;                        // ... reading $-: (row, input row) entries, their estart / heads
     DBuf inX, inLen, inT, inStr, inDesc;                // ... the pipe's input table
     uint64_t pipeWalks = 0;                             // walks run for FROM $- / $var sentences (flag pipe_walks)
+    // ngx_go_group_by: key table, leaders / flags / group numbers, COUNT_DISTINCT flags, state words, descriptors,
+    // string lengths and their scan, output cells and string bytes, scan tiles
+    DBuf gbTable, gbLeader, gbFlag, gbPre, gbDistinct, gbState, gbDesc, gbSlen, gbSpre, gbCells, gbStr, gbTiles;
+    hipEvent_t gbEv[2] = {nullptr, nullptr};            // ngx_group_result.device_ms: made on the first call, kept
+    uint64_t groupByDevice = 0, groupByLds = 0;        // calls completed on the device / through the LDS path
+    int64_t groupLdsMax = -1;                           // flag group_lds_max: -1 by size, else the largest group count
     DBuf localBits, pullGather;                         // world > 1 pull: this shard's frontier bitmap, all shards' 
     struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
     std::vector<ngx_stat> statList;                     // ngx_stats view
@@ -500,10 +506,12 @@ struct ngx_ctx {
         spaces.clear();
         for (DBuf* b : {&oEntry, &sendBits, &recvBits,
                         &vcells, &misc, &oFlags, &rowCols, &rowLen, &rowOff, &rowBytes, &dkTable, &dkKeep, &dkPre, &dSrc, &dDst,
-                        &dRank, &dType, &xListSend, &xListRecv, &xCounts}) b->release();
+                        &dRank, &dType, &xListSend, &xListRecv, &xCounts, &gbTable, &gbLeader, &gbFlag, &gbPre, &gbDistinct,
+                        &gbState, &gbDesc, &gbSlen, &gbSpre, &gbCells, &gbStr, &gbTiles}) b->release();
         for (auto& cb : dCols) { cb.x.release(); cb.len.release(); cb.t.release(); }
         hostStage.release();
         for (auto e : eventPool) (void)hipEventDestroy(e);
+        for (auto e : gbEv) if (e) (void)hipEventDestroy(e);
         for (auto e : pipeEv) if (e) (void)hipEventDestroy(e);
         for (auto e : laneCloseEv) if (e) (void)hipEventDestroy(e);
         for (auto e : pipeRing) if (e) (void)hipEventDestroy(e);
@@ -2113,6 +2121,7 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
         return NGX_OK;
     }
     if (n == "jit_wait") { c->jit.drain(); return NGX_OK; }
+    if (n == "group_lds_max") { c->groupLdsMax = value < 0 ? -1 : value; return NGX_OK; }
     return fail(c, NGX_E_BAD_ARGUMENT, "unknown flag " + n);
 }
 
@@ -2162,6 +2171,9 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "xchg_list_hops") *value = static_cast<int64_t>(c->xchgListHops);
     else if (n == "sparse_factor") *value = c->sparseFactor;
     else if (n == "pipe_walks") *value = static_cast<int64_t>(c->pipeWalks);
+    else if (n == "group_by_device") *value = static_cast<int64_t>(c->groupByDevice);
+    else if (n == "group_by_lds") *value = static_cast<int64_t>(c->groupByLds);
+    else if (n == "group_lds_max") *value = c->groupLdsMax;
     else if (n == "jit_compiled") *value = static_cast<int64_t>(c->jit.compiled);
     else if (n == "jit_hits") *value = static_cast<int64_t>(c->jit.hits);
     else if (n == "jit_cached") *value = static_cast<int64_t>(c->jit.size());
@@ -5650,4 +5662,277 @@ extern "C" int32_t ngx_stats(ngx_ctx* c, const ngx_stat** out, int32_t* n) {
     *out = c->statList.data();
     *n = static_cast<int32_t>(c->statList.size());
     return NGX_OK;
+}
+
+// ============================================================================ GROUP BY
+namespace {
+
+struct GroupResultHolder {
+    ngx_group_result r{};
+    std::vector<int32_t> colTypes;
+    std::vector<ngx_cell> cells;
+    std::string strings;
+};
+static_assert(sizeof(GroupCell) == sizeof(ngx_cell) && offsetof(GroupCell, v) == offsetof(ngx_cell, v), "GroupCell is ngx_cell");
+
+bool intLike(int32_t t) { return t == NGX_T_INT || t == NGX_T_VID || t == NGX_T_TIMESTAMP; }
+
+int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupResultHolder& R) {
+    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "group by: not a device-resident result");
+    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "group by: world > 1 needs mergeable partial states");
+    if (gp->nkeys < 1 || gp->nyields < 1 || !gp->key_cols || !gp->yields) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no key or yield columns");
+    if (gp->nkeys > kGroupMaxKeys) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 4 keys");
+    if (gp->nyields > kMaxDistinctCols) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 64 yields");
+    const uint64_t n = r->nrows;
+    if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "group by: 2^32 rows or more");
+
+    // the result columns the kernels read
+    std::vector<GroupCol> cols;
+    std::vector<int32_t> colOf(std::max<int32_t>(r->ncols, 1), -1), typeOf;
+    auto useCol = [&](int32_t y, bool key, int32_t* idx) -> int32_t {
+        if (y < 0 || y >= r->ncols) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no such result column");
+        const int32_t t = r->col_types[y];
+        if (t == 0 || (n && r->dev_cols[y].type)) return fail(c, NGX_E_UNSUPPORTED, "group by: UNKNOWN-typed column (per-row value types)");
+        if (t == NGX_T_FLOAT) return fail(c, NGX_E_UNSUPPORTED, "group by: FLOAT column");
+        if (key && t == NGX_T_DOUBLE) return fail(c, NGX_E_UNSUPPORTED, "group by: DOUBLE key column");
+        if (colOf[y] < 0) {
+            GroupCol gc{};
+            gc.kind = t == NGX_T_STRING ? kGroupString : t == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
+            gc.w = t == NGX_T_STRING || t == NGX_T_DOUBLE ? 8 : r->dev_col_w ? r->dev_col_w[y] : 8;
+            gc.konst = r->dev_col_const ? r->dev_col_const[y] : 0;
+            if (n) {
+                gc.x = gc.w ? r->dev_cols[y].x : nullptr;
+                gc.len = r->dev_cols[y].len;
+                if (gc.w && !gc.x) return fail(c, NGX_E_BAD_ARGUMENT, "group by: column without values");
+                if (gc.w != 0 && gc.w != 1 && gc.w != 2 && gc.w != 4 && gc.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "group by: column width");
+            }
+            colOf[y] = static_cast<int32_t>(cols.size());
+            cols.push_back(gc);
+            typeOf.push_back(t);
+        }
+        *idx = colOf[y];
+        return NGX_OK;
+    };
+    std::vector<int32_t> keyIdx(gp->nkeys);
+    for (int32_t k = 0; k < gp->nkeys; k++)
+        if (int32_t rc = useCol(gp->key_cols[k], true, &keyIdx[k])) return rc;
+
+    // per yield column: its state words and how its cell is finalised
+    std::vector<GroupSlot> slots;
+    std::vector<GroupEmit> emit(gp->nyields);
+    std::vector<int32_t> distinctCol;                            // value column of each COUNT_DISTINCT pass
+    auto slot = [&](int32_t op, int32_t src, int32_t col) {
+        GroupSlot s{};
+        s.op = op, s.src = src, s.col = col;
+        slots.push_back(s);
+        return static_cast<int32_t>(slots.size() - 1);
+    };
+    auto constant = [&](GroupEmit& e, int32_t kind, int64_t bits) { e.kind = kind, e.src = kEmitConst, e.konst = bits; };
+    for (int32_t y = 0; y < gp->nyields; y++) {
+        const ngx_agg_col& a = gp->yields[y];
+        GroupEmit& e = emit[y];
+        if (a.fn == NGX_AGG_STD) return fail(c, NGX_E_UNSUPPORTED, "group by: STD keeps every value of a group");
+        if (a.fn < NGX_AGG_GROUP || a.fn > NGX_AGG_BIT_XOR) return fail(c, NGX_E_BAD_ARGUMENT, "group by: unknown function");
+        int32_t ci = -1, t = 0;
+        if (a.col >= 0) {
+            if (int32_t rc = useCol(a.col, false, &ci)) return rc;
+            t = typeOf[ci];
+        } else {                                                  // a constant: a column of width 0
+            const int32_t k = a.konst.kind;
+            if (k != NGX_CELL_INT && k != NGX_CELL_DOUBLE && a.fn != NGX_AGG_COUNT && a.fn != NGX_AGG_COUNT_DISTINCT)
+                return fail(c, NGX_E_UNSUPPORTED, "group by: constant that is neither integer nor double");
+            t = k == NGX_CELL_INT ? NGX_T_INT : k == NGX_CELL_DOUBLE ? NGX_T_DOUBLE : NGX_T_STRING;
+            if (a.fn != NGX_AGG_GROUP && a.fn != NGX_AGG_COUNT && a.fn != NGX_AGG_COUNT_DISTINCT) {
+                GroupCol gc{};
+                gc.kind = t == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
+                gc.w = 0;
+                gc.konst = a.konst.v.i;
+                ci = static_cast<int32_t>(cols.size());
+                cols.push_back(gc);
+                typeOf.push_back(t);
+            }
+        }
+        switch (a.fn) {
+            case NGX_AGG_GROUP:
+                if (a.col < 0) { constant(e, a.konst.kind, a.konst.v.i); break; }
+                if (std::find(keyIdx.begin(), keyIdx.end(), ci) == keyIdx.end())
+                    return fail(c, NGX_E_UNSUPPORTED, "group by: a bare yield column that is not a key");
+                e.kind = t, e.src = kEmitKey, e.a = ci;
+                break;
+            case NGX_AGG_COUNT:
+                e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcOne, -1);
+                break;
+            case NGX_AGG_COUNT_DISTINCT:
+                if (a.col < 0) { constant(e, NGX_CELL_INT, 1); break; }
+                e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcFlag, static_cast<int32_t>(distinctCol.size()));
+                distinctCol.push_back(ci);
+                break;
+            case NGX_AGG_SUM:
+                if (intLike(t)) e.kind = t, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcCol, ci);
+                else if (t == NGX_T_DOUBLE) e.kind = NGX_CELL_DOUBLE, e.src = kEmitState, e.a = slot(kGroupAddF64, kGroupSrcCol, ci);
+                else constant(e, NGX_CELL_INT, 0);                // Sum ignores values it cannot add
+                break;
+            case NGX_AGG_AVG:
+                if (t == NGX_T_VID || t == NGX_T_TIMESTAMP)
+                    return fail(c, NGX_E_UNSUPPORTED, "group by: AVG of a VID / TIMESTAMP column (the reference reads the sum as a double)");
+                e.kind = NGX_CELL_DOUBLE;
+                if (t == NGX_T_INT) e.src = kEmitAvgInt, e.a = slot(kGroupAdd, kGroupSrcCol, ci), slot(kGroupAdd, kGroupSrcOne, -1);
+                else if (t == NGX_T_DOUBLE) e.src = kEmitAvgF64, e.a = slot(kGroupAddF64, kGroupSrcCol, ci), slot(kGroupAdd, kGroupSrcOne, -1);
+                else constant(e, NGX_CELL_DOUBLE, 0);             // 0 / count
+                break;
+            case NGX_AGG_MAX:
+            case NGX_AGG_MIN: {
+                const int32_t op = a.fn == NGX_AGG_MAX ? kGroupMax : kGroupMin;
+                if (intLike(t)) e.kind = t, e.src = kEmitState, e.a = slot(op, kGroupSrcCol, ci);
+                else if (t == NGX_T_DOUBLE) e.kind = NGX_CELL_DOUBLE, e.src = kEmitOrdered, e.a = slot(op, kGroupSrcOrdered, ci);
+                else return fail(c, NGX_E_UNSUPPORTED, "group by: MAX / MIN of a BOOL or STRING column");
+                break;
+            }
+            default:                                              // BIT_*: integers only, anything else is ignored
+                if (t == NGX_T_INT)
+                    e.kind = NGX_CELL_INT, e.src = kEmitState,
+                    e.a = slot(a.fn == NGX_AGG_BIT_AND ? kGroupAnd : a.fn == NGX_AGG_BIT_OR ? kGroupOr : kGroupXor, kGroupSrcCol, ci);
+                else constant(e, NGX_CELL_INT, 0);
+                break;
+        }
+    }
+    R.r.ncols = gp->nyields;
+    R.colTypes.assign(gp->nyields, 0);
+    R.r.col_types = R.colTypes.data();
+    if (n == 0) {
+        c->groupByDevice++;
+        return NGX_OK;
+    }
+    for (int32_t y = 0; y < gp->nyields; y++) R.colTypes[y] = emit[y].kind;
+
+    HIP_OK(hipSetDevice(c->device));
+    for (hipEvent_t& e : c->gbEv)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
+    HIP_OK(hipEventRecord(ev0, c->stream));
+
+    // ---- assign: leaders, group numbers
+    uint64_t cap = 1024;
+    while (cap < 2 * n) cap <<= 1;
+    GroupAssignArgs aa{};
+    aa.n = n;
+    aa.nk = gp->nkeys;
+    for (int32_t k = 0; k < gp->nkeys; k++) aa.k[k] = cols[keyIdx[k]];
+    aa.table = c->gbTable.get<uint64_t>(cap);
+    aa.mask = cap - 1;
+    aa.leader = c->gbLeader.get<uint32_t>(n);
+    aa.flag = c->gbFlag.get<uint64_t>(n + 1);
+    uint64_t* pre = c->gbPre.get<uint64_t>(n + 1);
+    uint64_t* tiles = c->gbTiles.get<uint64_t>((n + kTile - 1) / kTile + 1);
+    uint64_t* dflags = c->gbDistinct.get<uint64_t>(std::max<uint64_t>(distinctCol.size(), 1) * n);
+    c->timed("group_assign", n * 8 * static_cast<uint64_t>(gp->nkeys), [&] {
+        HIP_OK(hipMemsetAsync(aa.table, 0, cap * 8, c->stream));
+        if (launchGroupAssign(aa, c->stream)) throw Error{NGX_E_DEVICE, "group assign"};
+        if (launchScanU64(aa.flag, n, pre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "group scan"};
+        for (size_t d = 0; d < distinctCol.size(); d++) {         // (keys, value) leaders per COUNT_DISTINCT
+            GroupAssignArgs da = aa;
+            da.k[da.nk++] = cols[distinctCol[d]];
+            da.leader = nullptr;
+            da.flag = dflags + d * n;
+            HIP_OK(hipMemsetAsync(da.table, 0, cap * 8, c->stream));
+            if (launchGroupAssign(da, c->stream)) throw Error{NGX_E_DEVICE, "group distinct"};
+        }
+    });
+    const uint64_t ngroups = readScalar(c, pre + n);
+    if (ngroups == 0 || ngroups > n) throw Error{NGX_E_DEVICE, "group by: group count out of range"};
+
+    // ---- accumulate
+    const size_t descBytes = cols.size() * sizeof(GroupCol) + slots.size() * sizeof(GroupSlot) + emit.size() * sizeof(GroupEmit);
+    char* desc = c->gbDesc.get<char>(descBytes);
+    GroupCol* colsDev = reinterpret_cast<GroupCol*>(desc);
+    GroupSlot* slotsDev = reinterpret_cast<GroupSlot*>(colsDev + cols.size());
+    GroupEmit* emitDev = reinterpret_cast<GroupEmit*>(slotsDev + slots.size());
+    for (GroupSlot& s : slots)
+        if (s.src == kGroupSrcFlag) s.flag = dflags + static_cast<uint64_t>(s.col) * n;
+    HIP_OK(hipMemcpyAsync(colsDev, cols.data(), cols.size() * sizeof(GroupCol), hipMemcpyHostToDevice, c->stream));
+    if (!slots.empty())
+        HIP_OK(hipMemcpyAsync(slotsDev, slots.data(), slots.size() * sizeof(GroupSlot), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(emitDev, emit.data(), emit.size() * sizeof(GroupEmit), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vectors are pageable: copied before they go
+    GroupAccumArgs ga{};
+    ga.n = n;
+    ga.ngroups = ngroups;
+    ga.nslots = static_cast<int32_t>(slots.size());
+    ga.slots = slotsDev;
+    ga.cols = colsDev;
+    ga.leader = aa.leader;
+    ga.pre = pre;
+    ga.state = c->gbState.get<uint64_t>(std::max<uint64_t>(ngroups * slots.size(), 1));
+    const uint64_t stateBytes = ngroups * slots.size() * 8;
+    // LDS when the workgroup's copy is small next to the rows it folds (by default up to 32 KiB of state)
+    const bool lds = !slots.empty() && stateBytes <= kGroupLdsBytes &&
+                     (c->groupLdsMax < 0 ? stateBytes <= 32 * 1024 : ngroups <= static_cast<uint64_t>(c->groupLdsMax));
+    c->timed(lds ? "group_accum_lds" : "group_accum", n * 8 * (slots.size() + 1), [&] {
+        if (launchGroupAccum(ga, lds, c->stream)) throw Error{NGX_E_DEVICE, "group accumulate"};
+    });
+
+    // ---- emit
+    GroupEmitArgs ea{};
+    ea.n = n;
+    ea.ngroups = ngroups;
+    ea.ny = gp->nyields;
+    ea.emit = emitDev;
+    ea.cols = colsDev;
+    ea.flag = aa.flag;
+    ea.pre = pre;
+    ea.state = ga.state;
+    ea.cells = c->gbCells.get<GroupCell>(ngroups * gp->nyields);
+    bool anyString = false;
+    for (const GroupEmit& e : emit) anyString |= e.src == kEmitKey && cols[e.a].kind == kGroupString;
+    uint64_t strBytes = 0;
+    if (anyString) {
+        uint64_t* slen = c->gbSlen.get<uint64_t>(n + 1);
+        uint64_t* spre = c->gbSpre.get<uint64_t>(n + 1);
+        if (launchGroupStrLen(ea, slen, c->stream)) throw Error{NGX_E_DEVICE, "group string lengths"};
+        if (launchScanU64(slen, n, spre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "group string scan"};
+        strBytes = readScalar(c, spre + n);
+        ea.strPre = spre;
+        ea.strOut = c->gbStr.get<char>(std::max<uint64_t>(strBytes, 1));
+    }
+    c->timed("group_emit", ngroups * gp->nyields * sizeof(GroupCell), [&] {
+        if (launchGroupEmit(ea, c->stream)) throw Error{NGX_E_DEVICE, "group emit"};
+    });
+    HIP_OK(hipEventRecord(ev1, c->stream));
+    R.cells.resize(ngroups * gp->nyields);
+    HIP_OK(hipMemcpyAsync(R.cells.data(), ea.cells, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
+    R.strings.resize(strBytes);
+    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], ea.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+    c->collectTimings();
+    R.r.device_ms = ms;
+    R.r.ngroups = ngroups;
+    R.r.cells = R.cells.data();
+    R.r.strings = R.strings.data();
+    R.r.strings_len = strBytes;
+    c->groupByDevice++;
+    if (lds) c->groupByLds++;
+    return NGX_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t ngx_go_group_by(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* plan, ngx_group_result** out) {
+    if (!c || !r || !plan || !out) return NGX_E_BAD_ARGUMENT;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto R = std::make_unique<GroupResultHolder>();
+    int32_t rc;
+    try {
+        rc = groupBy(c, r, plan, *R);
+    } catch (const Error& e) {
+        rc = fail(c, e.code, e.msg);
+    }
+    R->r.code = rc;
+    *out = &R.release()->r;
+    return rc;
+}
+
+extern "C" void ngx_group_result_free(ngx_group_result* r) {
+    if (r) delete reinterpret_cast<GroupResultHolder*>(r);
 }

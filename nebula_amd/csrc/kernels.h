@@ -357,6 +357,81 @@ struct ScatterArgs {
     uint8_t esz[kMaxScatter];
 };
 int launchScatterKept(const ScatterArgs& a, hipStream_t s);
+// GROUP BY over a device-resident result (groupby.hip; ngx_go_group_by). A column as the kernels read it:
+// `w` bytes per element of x (1 / 2 / 4 signed, 8; 0: no array, every row holds konst); strings are
+// 8-byte device pointers with their lengths in len.
+constexpr int kGroupMaxKeys = 4;
+constexpr uint64_t kGroupLdsBytes = 64 * 1024;      // the LDS copy of the state one workgroup may hold
+enum { kGroupInt = 0, kGroupDouble = 1, kGroupString = 2 };
+struct GroupCol {
+    const void* x;
+    const uint32_t* len;
+    int64_t konst;
+    int32_t w;
+    int32_t kind;                       // kGroupInt (int / vid / timestamp / bool bits), kGroupDouble, kGroupString
+};
+// rows with equal values in the nk columns share a leader (the row that claimed their table slot):
+// flag[r] = 1 for leaders, leader[r] = the leader's row (may be null: only the flags are wanted).
+// table: capacity mask + 1 >= 2n, a power of two, zeroed.
+struct GroupAssignArgs {
+    uint64_t n;
+    int32_t nk;
+    GroupCol k[kGroupMaxKeys + 1];      // the keys, plus the value column of a COUNT_DISTINCT pass
+    uint64_t* table;
+    uint64_t mask;
+    uint32_t* leader;
+    uint64_t* flag;
+};
+int launchGroupAssign(const GroupAssignArgs& a, hipStream_t s);
+// one 64-bit state word per (slot, group): state[slot * ngroups + g] op= the row's value
+enum { kGroupAdd = 0, kGroupAddF64, kGroupAnd, kGroupOr, kGroupXor, kGroupMax, kGroupMin };
+enum { kGroupSrcOne = 0, kGroupSrcCol, kGroupSrcOrdered, kGroupSrcFlag };   // 1, cols[col], its order key (double), flag[r]
+struct GroupSlot {
+    int32_t op;
+    int32_t src;
+    int32_t col;
+    int32_t pad;
+    const uint64_t* flag;
+};
+struct GroupAccumArgs {
+    uint64_t n, ngroups;
+    int32_t nslots;
+    const GroupSlot* slots;             // device arrays
+    const GroupCol* cols;
+    const uint32_t* leader;
+    const uint64_t* pre;                // exclusive scan of the leader flags: pre[leader row] = group id
+    uint64_t* state;                    // nslots * ngroups words, initialised by the launcher
+};
+// lds: every workgroup aggregates into an LDS copy of the state (nslots * ngroups * 8 <= kGroupLdsBytes)
+int launchGroupAccum(const GroupAccumArgs& a, bool lds, hipStream_t s);
+// one output cell per (group, yield column), laid out as ngx_cell
+struct GroupCell {
+    int32_t kind;
+    int32_t len;
+    int64_t v;                          // value bits, or the offset of a string's bytes in strOut
+};
+enum { kEmitKey = 0, kEmitState, kEmitOrdered, kEmitAvgInt, kEmitAvgF64, kEmitConst };
+struct GroupEmit {
+    int32_t kind;                       // NGX_CELL_*
+    int32_t src;                        // kEmit*
+    int32_t a;                          // kEmitKey: column; state kinds: slot (AVG: sum slot, count slot + 1)
+    int32_t pad;
+    int64_t konst;
+};
+struct GroupEmitArgs {
+    uint64_t n, ngroups;
+    int32_t ny;
+    const GroupEmit* emit;              // device arrays
+    const GroupCol* cols;
+    const uint64_t* flag;
+    const uint64_t* pre;
+    const uint64_t* state;
+    const uint64_t* strPre;             // exclusive scan of launchGroupStrLen's lengths; null: no string cells
+    char* strOut;
+    GroupCell* cells;                   // ngroups * ny
+};
+int launchGroupStrLen(const GroupEmitArgs& a, uint64_t* slen, hipStream_t s);
+int launchGroupEmit(const GroupEmitArgs& a, hipStream_t s);
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

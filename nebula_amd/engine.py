@@ -157,6 +157,31 @@ class GoResultC(ctypes.Structure):
                 ("dev_key_const", c_i64 * 3), ("dev_col_const", P(c_i64))]
 
 
+AGG_FN = {"": 0, "COUNT": 1, "COUNT_DISTINCT": 2, "SUM": 3, "AVG": 4, "MAX": 5, "MIN": 6, "STD": 7, "BIT_AND": 8,
+          "BIT_OR": 9, "BIT_XOR": 10}                              # NGX_AGG_*
+
+
+class AggColC(ctypes.Structure):
+    _fields_ = [("fn", c_i32), ("col", c_i32), ("konst", Cell)]
+
+
+class GroupPlanC(ctypes.Structure):
+    _fields_ = [("nkeys", c_i32), ("key_cols", P(c_i32)), ("nyields", c_i32), ("yields", P(AggColC))]
+
+
+class GroupResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("ngroups", c_u64), ("cells", P(Cell)),
+                ("strings", ctypes.c_void_p), ("strings_len", c_u64), ("device_ms", c_dbl)]
+
+
+@dataclass
+class GroupBySpec:
+    """ngx_group_plan: key columns and yield columns (function name, GO YIELD column or -1, constant) by
+    GO YIELD index. A constant is an int, a float, or "*"."""
+    key_cols: List[int]
+    yields: List[Tuple[str, int, object]]
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -187,6 +212,8 @@ SIGNATURES = {
     "ngx_set_profiling": (c_i32, [ctypes.c_void_p, c_i32]),
     "ngx_synchronize": (c_i32, [ctypes.c_void_p]),
     "ngx_go_result_digest": (c_i32, [ctypes.c_void_p, P(GoResultC), P(c_u64)]),
+    "ngx_go_group_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GroupPlanC), P(P(GroupResultC))]),
+    "ngx_group_result_free": (None, [P(GroupResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
     "ngx_kernel_stats": (c_i32, [ctypes.c_void_p, P(P(KernelStat)), P(c_i32)]),
     "ngx_set_flag": (c_i32, [ctypes.c_void_p, ctypes.c_char_p, c_i64]),
@@ -309,6 +336,10 @@ class GoResult:
     device_digest: Optional[tuple] = None  # on_device + device_digest: (sum, xor, rows) of the row hashes
     host_prep_ms: float = 0.0            # library host time before the first launch / after the device
     host_tail_ms: float = 0.0
+    # group_by: the traversal's device time and row count, and the grouping's device time
+    go_device_ms: float = 0.0
+    go_nrows: int = 0
+    group_device_ms: float = 0.0
 
 
 @dataclass
@@ -347,6 +378,8 @@ class PreparedGo:
 
 
 class Engine:
+    device_group_by = True                     # go(..., group_by=...) groups a device-resident result (pipeline.py)
+
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
         """world > 1: one shard per rank over RCCL (nccl_id from unique_id() on rank 0), or over a host
@@ -497,7 +530,8 @@ class Engine:
     def go(self, space: int, s: Union[str, ngql.GoSentence], pushdown: bool = True, now_sec: int = 0,
            raise_on_error: bool = False, rows: bool = True, on_device: bool = False, fetch: bool = False,
            columnar: bool = False, digest_fn=None, arrays: bool = True, input=None,
-           yield_only: bool = False, compact: bool = False, device_digest: bool = False) -> GoResult:
+           yield_only: bool = False, compact: bool = False, device_digest: bool = False,
+           group_by: Optional[GroupBySpec] = None) -> GoResult:
         """Run one GO. rows=False skips decoding cells into Python tuples; on_device=True leaves the
         result rows in HBM (GoResult.nrows and the statistics only); with fetch=True the HBM arrays
         (src/dst/rank/type and the columnar YIELD columns) are copied back into the result.
@@ -510,7 +544,13 @@ class Engine:
         device_digest (with on_device): GoResult.device_digest = (sum, xor, rows) of the row hashes, computed
         on the device (ngx_go_result_digest; oracle.row_digest restates it).
         compact (with on_device): integer result arrays at the widths of the stored columns they copy
-        (ngx_go_plan.compact_results); fetch widens them back to int64 (GoResult.dev_widths keeps them)."""
+        (ngx_go_plan.compact_results); fetch widens them back to int64 (GoResult.dev_widths keeps them).
+        group_by: the GO runs with on_device and its rows are grouped in HBM (ngx_go_group_by) before the
+        result is freed; GoResult.rows / col_types / nrows are then the group rows, device_ms the grouping's
+        and group_device_ms too (go_device_ms keeps the traversal's). NGX_E_UNSUPPORTED comes back as a
+        result with that code and the reason (the caller groups on the host), not as an exception."""
+        if group_by is not None:
+            on_device, columnar = True, False
         if isinstance(s, PreparedGo):                       # its own pushdown / result-placement flags
             plan, keep = s.plan, s
             on_device, columnar = bool(plan.result_on_device), bool(plan.host_columnar)
@@ -545,6 +585,8 @@ class Engine:
                     # width 0: a constant column (value in dev_key_const / dev_col_const, no array)
                     res.dev_widths = (r.dev_key_w[:3], r.dev_col_w[:nc] if nc else [])
                     res.dev_consts = (r.dev_key_const[:3], r.dev_col_const[:nc] if nc and r.dev_col_const else [0] * nc)
+                if group_by is not None and rc == 0:
+                    self._group_by(out, group_by, res)
                 if device_digest and rc == 0:
                     d3 = (c_u64 * 3)()
                     drc = self.L.ngx_go_result_digest(self.h, out, d3)
@@ -591,6 +633,38 @@ class Engine:
             return res
         finally:
             self.L.ngx_go_result_free(out)
+
+    def _group_by(self, go_out, spec: GroupBySpec, res: GoResult):
+        keys = (c_i32 * max(1, len(spec.key_cols)))(*spec.key_cols)
+        ys = (AggColC * max(1, len(spec.yields)))()
+        for i, (fn, col, konst) in enumerate(spec.yields):
+            ys[i].fn, ys[i].col = AGG_FN[fn], col
+            if col < 0:
+                if isinstance(konst, float):
+                    ys[i].konst.kind, ys[i].konst.v.d = _CELL_KIND["double"], konst
+                elif isinstance(konst, int) and not isinstance(konst, bool):
+                    ys[i].konst.kind, ys[i].konst.v.i = _CELL_KIND["int"], konst
+                else:
+                    ys[i].konst.kind = _CELL_KIND["str"]
+        plan = GroupPlanC(len(spec.key_cols), keys, len(spec.yields), ys)
+        gout = P(GroupResultC)()
+        rc = self.L.ngx_go_group_by(self.h, go_out, ctypes.byref(plan), ctypes.byref(gout))
+        try:
+            res.go_device_ms, res.go_nrows = res.device_ms, res.nrows
+            if rc:
+                err = self.L.ngx_last_error(self.h).decode()
+                if rc != E_UNSUPPORTED:
+                    raise EngineError(rc, err)
+                res.ok, res.code, res.error = False, rc, err
+                return
+            g = gout.contents
+            strings = ctypes.string_at(g.strings, g.strings_len) if g.strings_len else b""
+            res.rows = _cells(g.cells, g.ngroups, g.ncols, strings)
+            res.col_types = g.col_types[:g.ncols] if g.ngroups else []
+            res.nrows = g.ngroups
+            res.device_ms = res.group_device_ms = g.device_ms
+        finally:
+            self.L.ngx_group_result_free(gout)
 
     def go_batch(self, prepared: Sequence["PreparedGo"], digests: bool = False):
         """Run prepared GO plans back to back in one native call (ngx_go_batch): per query (code, result

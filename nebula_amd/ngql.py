@@ -577,3 +577,72 @@ def parse_go(src: str) -> GoSentence:
             s.yields.append(YieldCol(Prop(K_EDGE_DST, "", name, "_dst")))
     p.expect("eof")
     return s
+
+
+# ------------------------------------------------------------------------------ GROUP BY sentence
+# agg_function (parser.yy:318-329); the keywords are case-insensitive in the scanner
+AGG_FUNCS = ("COUNT", "COUNT_DISTINCT", "SUM", "AVG", "MAX", "MIN", "STD", "BIT_AND", "BIT_OR", "BIT_XOR")
+
+
+@dataclass
+class AggCol:
+    """A yield_column of a GROUP BY sentence (parser.yy:763-792): an expression, an optional aggregate
+    function name around it and an optional alias. `*' is PrimaryExpression("*")."""
+    expr: Expr
+    alias: str = ""
+    fun: str = ""
+
+    def to_string(self) -> str:                                   # YieldColumn::toString, Clauses.cpp:194-207
+        return self.fun + "(" + self.expr.to_string() + ")" if self.fun else self.expr.to_string()
+
+
+@dataclass
+class GroupBySentence:
+    """Parsed `GROUP BY <cols> YIELD <cols>` (group_by_sentence, parser.yy:1013-1020)."""
+    groups: List[AggCol] = field(default_factory=list)
+    yields: List[AggCol] = field(default_factory=list)
+
+    def column_names(self) -> List[str]:
+        """GroupByExecutor::getResultColumnNames (GroupByExecutor.cpp:334-345)."""
+        return [y.alias if y.alias else y.to_string() for y in self.yields]
+
+
+def _agg_columns(p: Parser, stop: str = "") -> List[AggCol]:
+    cols = []
+    while p.peek().kind != "eof" and not (stop and p.is_kw(stop)):
+        t = p.peek()
+        fun = ""
+        if t.kind == "name" and t.text.upper() in AGG_FUNCS and p.peek(1).kind == "op" and p.peek(1).text == "(":
+            fun = p.take().text.upper()
+            p.take()
+            if p.is_op("*") and p.peek(1).kind == "op" and p.peek(1).text == ")":
+                p.take()
+                e = Prim("*")
+            else:
+                e = p.expression()
+            p.expect("op", ")")
+        else:
+            e = p.expression()
+        alias = p.label() if p.accept("kw", "AS") else ""
+        cols.append(AggCol(e, alias, fun))
+        if not p.accept("op", ","):
+            break
+    return cols
+
+
+def is_group_by(src: str) -> bool:
+    return re.match(r"\s*GROUP\s+BY\b", src, re.I) is not None
+
+
+def parse_group_by(src: str) -> GroupBySentence:
+    p = Parser(src)
+    for word in ("GROUP", "BY"):
+        t = p.take()
+        if t.kind != "name" or t.text.upper() != word:
+            raise SyntaxError(f"expected {word}, got {t.text!r}")
+    s = GroupBySentence()
+    s.groups = _agg_columns(p, "YIELD")
+    if p.accept("kw", "YIELD"):
+        s.yields = _agg_columns(p)
+    p.expect("eof")
+    return s

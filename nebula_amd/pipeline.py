@@ -11,7 +11,9 @@ library, include/nebula_gn.h ngx_go with input_* set):
     column's calculateExprType, or for UNKNOWN the variant type of the first record;
   - YieldClauseWrapper::prepare (TraverseExecutor.cpp:344-392): `$-.*` / `$v.*` in YIELD expands to
     every input column.
-Only GO sentences are traversal sentences here (the other executors are outside the GO path).
+  - GroupByExecutor (src/graph/GroupByExecutor.cpp): `... | GROUP BY <cols> YIELD <aggregates>` over the
+    left side's interim result (nebula_amd/groupby.py).
+GO and GROUP BY are the traversal sentences here (ORDER BY, LIMIT and `| YIELD` are outside this path).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
 """
 from __future__ import annotations
@@ -19,7 +21,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-from . import ngql
+from . import groupby, ngql
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
 _KIND_TYPE = {"bool": T_BOOL, "int": T_INT, "id": T_INT, "timestamp": T_INT, "float": T_DOUBLE,
@@ -125,7 +127,9 @@ class Outcome:
 class Pipeline:
     """Runs nGQL text made of GO sentences, pipes, parentheses, `$v = ...' and `;'."""
 
-    def __init__(self, backend, space: int, edge_names: Sequence[str] = (), **go_kw):
+    def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True, **go_kw):
+        """device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device."""
+        self.device_group_by = device_group_by
         self.backend = backend
         self.space = space
         self.edge_names = list(edge_names)
@@ -137,6 +141,9 @@ class Pipeline:
             s = ngql.parse_go(text)
         except (SyntaxError, ValueError) as e:
             return Outcome(False, "SyntaxError: %s" % e)
+        for y in s.yields:                                        # GoExecutor::prepareYield, GoExecutor.cpp:343-347
+            if isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS:
+                return Outcome(False, "SyntaxError: Do not support in aggregated query without group by")
         feed = None
         if s.from_type == 1:
             feed = inp if inp is not None else Interim([])
@@ -192,16 +199,101 @@ class Pipeline:
         types = [_KIND_TYPE[k] for k, _ in row]
         return Outcome(True, "", names, types, [tuple(row)])
 
+    def _device_spec(self, go_text: str, gb_text: str):
+        """(GoSentence, GroupBySentence, spec) when `GO | GROUP BY` can group on the device (ngx_go_group_by):
+        a plain GO (literal vids, no DISTINCT, no $- / $var), keys that are input columns, yields that are
+        input columns or constants, no STD. None: the host path decides (and reports any error)."""
+        from .engine import GroupBySpec
+        try:
+            s, g = ngql.parse_go(go_text), ngql.parse_group_by(gb_text)
+            aliases = groupby.prepare(g)
+            names = s.column_names(self.edge_names)
+            if s.from_type or s.distinct or not s.yields or len(set(names)) != len(names):
+                return None
+            for y in s.yields:
+                if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
+                        any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
+                    return None
+            groups = groupby.check_all(g, aliases, names)
+            if len(groups) > 4 or not all(groupby._is_input(c.expr) for c in groups):
+                return None
+            yields = []
+            for y in g.yields:
+                if y.fun == "STD":
+                    return None
+                if groupby._is_input(y.expr):
+                    yields.append((y.fun, names.index(y.expr.prop), None))
+                    continue
+                if y.expr.props():
+                    return None
+                v, _ = groupby._eval(y.expr, (), {})
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    if not (isinstance(v, str) and y.fun in ("COUNT", "COUNT_DISTINCT")):
+                        return None
+                    v = "*"
+                yields.append((y.fun, -1, v))
+            return s, g, GroupBySpec([names.index(c.expr.prop) for c in groups], yields)
+        except (SyntaxError, ValueError, groupby.GroupByError):
+            return None
+
+    def _go_group_by(self, go_text: str, gb_text: str) -> Optional[Outcome]:
+        """`GO | GROUP BY` with the grouping on the device; None when the host path has to run."""
+        plan = self._device_spec(go_text, gb_text)
+        if plan is None:
+            return None
+        s, g, spec = plan
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            r = self.backend.go(self.space, s, group_by=spec, yield_only=True, compact=True, **kw)
+        except RuntimeError as e:
+            if getattr(e, "code", 0) == -1002:                    # the device-resident GO itself: the plain path decides
+                return None
+            raise
+        if not r.ok:
+            if r.code == -1002:                                   # NGX_E_UNSUPPORTED: group on the host
+                return None
+            return Outcome(False, r.error, s.column_names(self.edge_names))
+        return Outcome(True, "", g.column_names(), list(r.col_types), list(r.rows))
+
+    def _group_by(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """A GROUP BY sentence on the pipe's input: GroupByExecutor restated on the host (groupby.run)."""
+        try:
+            s = ngql.parse_group_by(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        inp = inp if inp is not None else Interim([])
+        try:
+            names, types, rows = groupby.run(s, inp.names, inp.types, inp.rows)
+        except groupby.GroupByError as e:
+            return Outcome(False, str(e), s.column_names())
+        return Outcome(True, "", names, types, rows)
+
     def _piped(self, text: str, inp: Optional[Interim]) -> Outcome:
         parts = _split(text, "|")
         cur = inp
         out = None
+        skip = False
         for i, part in enumerate(parts):
             body = _unwrap(part)
+            if skip:                                              # grouped on the device with the GO before it
+                skip = False
+                if i + 1 < len(parts):
+                    cur = Interim.from_result(out.names, out.col_types, out.rows)
+                continue
+            if self.device_group_by and getattr(self.backend, "device_group_by", False) and i + 1 < len(parts) \
+                    and body.upper().startswith("GO") and ngql.is_group_by(_unwrap(parts[i + 1])):
+                dev = self._go_group_by(body, _unwrap(parts[i + 1]))
+                if dev is not None:
+                    out, skip = dev, True
+                    if not out.ok:
+                        return out
+                    continue
             if len(_split(body, "|")) > 1:
                 out = self._piped(body, cur)                      # ( set_sentence ) as a traverse sentence
             elif body.upper().startswith("YIELD") and cur is None:
                 out = self._yield_constant(body)
+            elif ngql.is_group_by(body):
+                out = self._group_by(body, cur)
             else:
                 if not body.upper().startswith("GO"):
                     raise PipelineError("only GO sentences run in this path: " + body[:40])
@@ -231,5 +323,5 @@ class Pipeline:
         return out
 
 
-def run(backend, space: int, text: str, edge_names: Sequence[str] = (), **go_kw) -> Outcome:
-    return Pipeline(backend, space, edge_names, **go_kw).run(text)
+def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True, **go_kw) -> Outcome:
+    return Pipeline(backend, space, edge_names, device_group_by=device_group_by, **go_kw).run(text)
