@@ -460,6 +460,54 @@ typedef struct {
 int32_t ngx_go_group_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_group_plan* plan, ngx_group_result** out);
 void ngx_group_result_free(ngx_group_result* r);
 
+/* ---------------------------------------------------------------- ORDER BY / LIMIT over a GO result */
+/* `GO ... | ORDER BY <factors> | LIMIT [off,] n` (and `GO ... | LIMIT [off,] n`) with the selection on the
+ * device: replaces OrderByExecutor's sort (src/graph/OrderByExecutor.cpp:88-109) and LimitExecutor's window
+ * (src/graph/LimitExecutor.cpp:52-61) for a result that stayed in HBM. Only the cells and string bytes of
+ * the offset + count first rows of the order cross PCIe. `r` is a result_on_device result of this context,
+ * and the call comes before any other call on the context (as ngx_go_group_by). Factors name GO YIELD
+ * columns; the result holds every GO YIELD column of rows [offset, offset + count) of the ordered result,
+ * as cells in order (col_types: the GO's).
+ * Order: the factors in turn, each ascending or descending, compared as ColumnValue::operator< does: INT /
+ * VID / TIMESTAMP as signed 64-bit, BOOL false < true, DOUBLE by value (-0.0 equals 0.0; a NaN, which the
+ * reference's comparator leaves undefined, is placed by its bits: positive NaNs after +inf, negative ones
+ * before -inf), STRING as unsigned bytes with a proper prefix first. The reference sorts with std::sort, so
+ * rows equal on every factor have no fixed order there; here the row's index in the device result is the
+ * last, ascending key, which makes the order total: the answer is one valid outcome of the reference's sort.
+ * The device selects the offset + count first rows (a radix select over the factor columns, read in place);
+ * the library orders those winners on the host with one std::sort (host_sort_ms) and drops the first
+ * `offset`. With no factors (LIMIT alone) the rows [offset, offset + count) come out as stored.
+ * NGX_E_UNSUPPORTED, with the reason in ngx_last_error, for: count < 0 (ORDER BY without LIMIT: every row
+ * crosses anyway), offset + count above the flag "order_k_max" (default 65536), a factor column of UNKNOWN
+ * (per-row) type, more than 8 factors, a factor string longer than 256 bytes, world > 1 (the shards'
+ * winners are not merged yet). The caller then orders on the host. A count of 0 or an offset at or past the
+ * end answers with no rows and launches nothing.
+ * Flags: "order_by_device" counts the calls completed on the device; "order_k_max" is settable. */
+typedef struct {
+    int32_t col;                       /* GO YIELD column */
+    int32_t desc;                      /* 0 ASC, 1 DESC */
+} ngx_order_factor;
+typedef struct {
+    int32_t nfactors;                  /* 0: LIMIT alone */
+    const ngx_order_factor* factors;
+    int64_t offset;
+    int64_t count;                     /* < 0: no LIMIT */
+} ngx_order_plan;
+typedef struct {
+    int32_t code;
+    int32_t ncols;                     /* the GO's YIELD columns */
+    const int32_t* col_types;          /* NGX_T_* per column, as the GO result's col_types */
+    uint64_t nrows;
+    const ngx_cell* cells;             /* cells[row * ncols + col] */
+    const char* strings;
+    uint64_t strings_len;
+    uint64_t input_rows;               /* rows of the GO result */
+    double device_ms;                  /* HIP-event time of the selection, first kernel to the last cell */
+    double host_sort_ms;               /* host time ordering the winners after the copy */
+} ngx_order_result;
+int32_t ngx_go_order_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_order_plan* plan, ngx_order_result** out);
+void ngx_order_result_free(ngx_order_result* r);
+
 /* ---------------------------------------------------------------- measurement hooks */
 /* Per-kernel device times of the last ngx_go (HIP events on the engine stream), for bench.py. */
 typedef struct {

@@ -233,9 +233,14 @@ struct ngx_ctx {
     // ngx_go_group_by: key table, leaders / flags / group numbers, COUNT_DISTINCT flags, state words, descriptors,
     // string lengths and their scan, output cells and string bytes, scan tiles
     DBuf gbTable, gbLeader, gbFlag, gbPre, gbDistinct, gbState, gbDesc, gbSlen, gbSpre, gbCells, gbStr, gbTiles;
-    hipEvent_t gbEv[2] = {nullptr, nullptr};            // ngx_group_result.device_ms: made on the first call, kept
+    hipEvent_t gbEv[2] = {nullptr, nullptr};            // ngx_group_result / ngx_order_result.device_ms: made on the first call, kept
     uint64_t groupByDevice = 0, groupByLds = 0;        // calls completed on the device / through the LDS path
     int64_t groupLdsMax = -1;                           // flag group_lds_max: -1 by size, else the largest group count
+    // ngx_go_order_by: row marks, the two tied-row lists, digit counters, state, descriptors, string-length maxima,
+    // winners' rows, their string lengths and scan, output cells and string bytes, scan tiles
+    DBuf obMark, obList[2], obHist, obState, obDesc, obMax, obWin, obSlen, obSpre, obCells, obStr, obTiles;
+    uint64_t orderByDevice = 0;                         // calls completed on the device (flag order_by_device)
+    int64_t orderKMax = 65536;                          // flag order_k_max: the largest offset + count selected on the device
     DBuf localBits, pullGather;                         // world > 1 pull: this shard's frontier bitmap, all shards' 
     struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
     std::vector<ngx_stat> statList;                     // ngx_stats view
@@ -507,7 +512,8 @@ struct ngx_ctx {
         for (DBuf* b : {&oEntry, &sendBits, &recvBits,
                         &vcells, &misc, &oFlags, &rowCols, &rowLen, &rowOff, &rowBytes, &dkTable, &dkKeep, &dkPre, &dSrc, &dDst,
                         &dRank, &dType, &xListSend, &xListRecv, &xCounts, &gbTable, &gbLeader, &gbFlag, &gbPre, &gbDistinct,
-                        &gbState, &gbDesc, &gbSlen, &gbSpre, &gbCells, &gbStr, &gbTiles}) b->release();
+                        &gbState, &gbDesc, &gbSlen, &gbSpre, &gbCells, &gbStr, &gbTiles, &obMark, &obList[0], &obList[1],
+                        &obHist, &obState, &obDesc, &obMax, &obWin, &obSlen, &obSpre, &obCells, &obStr, &obTiles}) b->release();
         for (auto& cb : dCols) { cb.x.release(); cb.len.release(); cb.t.release(); }
         hostStage.release();
         for (auto e : eventPool) (void)hipEventDestroy(e);
@@ -2122,6 +2128,11 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
     }
     if (n == "jit_wait") { c->jit.drain(); return NGX_OK; }
     if (n == "group_lds_max") { c->groupLdsMax = value < 0 ? -1 : value; return NGX_OK; }
+    if (n == "order_k_max") {
+        if (value < 1 || value > (int64_t(1) << 24)) return fail(c, NGX_E_BAD_ARGUMENT, "order_k_max: 1 .. 2^24");
+        c->orderKMax = value;
+        return NGX_OK;
+    }
     return fail(c, NGX_E_BAD_ARGUMENT, "unknown flag " + n);
 }
 
@@ -2174,6 +2185,8 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "group_by_device") *value = static_cast<int64_t>(c->groupByDevice);
     else if (n == "group_by_lds") *value = static_cast<int64_t>(c->groupByLds);
     else if (n == "group_lds_max") *value = c->groupLdsMax;
+    else if (n == "order_by_device") *value = static_cast<int64_t>(c->orderByDevice);
+    else if (n == "order_k_max") *value = c->orderKMax;
     else if (n == "jit_compiled") *value = static_cast<int64_t>(c->jit.compiled);
     else if (n == "jit_hits") *value = static_cast<int64_t>(c->jit.hits);
     else if (n == "jit_cached") *value = static_cast<int64_t>(c->jit.size());
@@ -5935,4 +5948,263 @@ extern "C" int32_t ngx_go_group_by(ngx_ctx* c, const ngx_go_result* r, const ngx
 
 extern "C" void ngx_group_result_free(ngx_group_result* r) {
     if (r) delete reinterpret_cast<GroupResultHolder*>(r);
+}
+
+// ============================================================================ ORDER BY / LIMIT
+namespace {
+
+struct OrderResultHolder {
+    ngx_order_result r{};
+    std::vector<int32_t> colTypes;
+    std::vector<ngx_cell> cells;
+    std::string strings;
+};
+
+// the word the device orders a double by (orderby.hip kOrdDouble): the winners' host sort uses the same
+uint64_t orderDoubleKey(int64_t bits) {
+    uint64_t b = static_cast<uint64_t>(bits);
+    double d;
+    std::memcpy(&d, &b, sizeof d);
+    if (d == 0.0) b = 0;
+    return b ^ (static_cast<uint64_t>(static_cast<int64_t>(b) >> 63) | 0x8000000000000000ULL);
+}
+
+int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, OrderResultHolder& R) {
+    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "order by: not a device-resident result");
+    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "order by: world > 1 needs the shards' winners merged");
+    if (op->nfactors < 0 || (op->nfactors && !op->factors) || op->offset < 0) return fail(c, NGX_E_BAD_ARGUMENT, "order by: factors or offset");
+    if (op->count < 0) return fail(c, NGX_E_UNSUPPORTED, "order by: no LIMIT (every row crosses anyway)");
+    if (op->nfactors > kOrderMaxFactors) return fail(c, NGX_E_UNSUPPORTED, "order by: more than 8 factors");
+    if (op->offset > c->orderKMax || op->count > c->orderKMax - op->offset)
+        return fail(c, NGX_E_UNSUPPORTED, "order by: offset + count above order_k_max");
+    const uint64_t n = r->nrows;
+    if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "order by: 2^32 rows or more");
+    const int32_t ncols = r->ncols;
+    for (int32_t f = 0; f < op->nfactors; f++) {
+        const int32_t y = op->factors[f].col;
+        if (y < 0 || y >= ncols) return fail(c, NGX_E_BAD_ARGUMENT, "order by: no such result column");
+        if (r->col_types[y] == 0 || (n && r->dev_cols[y].type))
+            return fail(c, NGX_E_UNSUPPORTED, "order by: UNKNOWN-typed factor column (per-row value types)");
+    }
+    R.r.input_rows = n;
+    R.r.ncols = ncols;
+    R.colTypes.assign(r->col_types, r->col_types + ncols);
+    R.r.col_types = R.colTypes.data();
+    const uint64_t offset = static_cast<uint64_t>(op->offset), K = offset + static_cast<uint64_t>(op->count);
+    if (op->count == 0 || offset >= n || ncols == 0) {           // the column names and no rows: nothing to launch
+        c->orderByDevice++;
+        return NGX_OK;
+    }
+
+    // every column as the emit kernel reads it; the factors' among them feed the levels
+    std::vector<OrderEmitCol> ecols(ncols);
+    std::vector<GroupCol> cols(ncols);
+    bool anyString = false;
+    for (int32_t y = 0; y < ncols; y++) {
+        const int32_t t = r->col_types[y];
+        OrderEmitCol& e = ecols[y];
+        e.type = r->dev_cols[y].type;
+        if (t == 0 && !e.type) return fail(c, NGX_E_UNSUPPORTED, "order by: a column of UNKNOWN type without per-row types");
+        e.cell = t;                                               // NGX_CELL_* numbers its kinds as NGX_T_*
+        e.c.kind = t == NGX_T_STRING ? kGroupString : t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? kGroupDouble : kGroupInt;
+        e.c.w = e.type || t == NGX_T_STRING || t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? 8 : r->dev_col_w ? r->dev_col_w[y] : 8;
+        e.c.konst = r->dev_col_const ? r->dev_col_const[y] : 0;
+        e.c.x = e.c.w ? r->dev_cols[y].x : nullptr;
+        e.c.len = r->dev_cols[y].len;
+        if (e.c.w && !e.c.x) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column without values");
+        if (e.c.w != 0 && e.c.w != 1 && e.c.w != 2 && e.c.w != 4 && e.c.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column width");
+        anyString |= t == NGX_T_STRING || e.type != nullptr;
+        cols[y] = e.c;
+    }
+
+    HIP_OK(hipSetDevice(c->device));
+    for (hipEvent_t& e : c->gbEv)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
+    HIP_OK(hipEventRecord(ev0, c->stream));
+
+    // ---- the levels: per factor its words, then the row index
+    std::vector<OrderLevel> levels;
+    auto bitsFor = [](uint64_t maxValue) {
+        int32_t bits = 8;
+        while (bits < 64 && (maxValue >> bits)) bits += 8;
+        return bits;
+    };
+    for (int32_t f = 0; f < op->nfactors; f++) {
+        const int32_t y = op->factors[f].col, t = r->col_types[y];
+        const int32_t desc = op->factors[f].desc ? 1 : 0;
+        if (t == NGX_T_STRING) {
+            uint32_t* mx = c->obMax.get<uint32_t>(1);
+            if (launchOrderMaxLen(cols[y].len, n, mx, c->stream)) throw Error{NGX_E_DEVICE, "order max length"};
+            const uint32_t maxLen = readScalar(c, mx);
+            if (maxLen > kOrderMaxStr) return fail(c, NGX_E_UNSUPPORTED, "order by: a factor string longer than 256 bytes");
+            for (uint32_t w = 0; w < (maxLen + 7) / 8; w++) levels.push_back(OrderLevel{y, kOrdStrWord, static_cast<int32_t>(w), desc, 64, 0});
+            if (maxLen) levels.push_back(OrderLevel{y, kOrdStrLen, 0, desc, bitsFor(maxLen), 0});
+        } else if (t == NGX_T_DOUBLE || t == NGX_T_FLOAT) {
+            levels.push_back(OrderLevel{y, kOrdDouble, 0, desc, 64, 0});
+        } else if (cols[y].w) {                                   // width 0: a constant ties every row
+            levels.push_back(OrderLevel{y, kOrdInt, 0, desc, cols[y].w * 8, 0});
+        }
+    }
+    const bool select = !levels.empty() && K < n;                 // else the winners are a range of rows as stored
+    levels.push_back(OrderLevel{0, kOrdRow, 0, 0, bitsFor(n - 1), 0});
+
+    // ---- descriptors
+    const size_t descBytes = cols.size() * sizeof(GroupCol) + ecols.size() * sizeof(OrderEmitCol) + levels.size() * sizeof(OrderLevel);
+    char* desc = c->obDesc.get<char>(descBytes);
+    OrderEmitCol* ecolsDev = reinterpret_cast<OrderEmitCol*>(desc);
+    GroupCol* colsDev = reinterpret_cast<GroupCol*>(ecolsDev + ecols.size());
+    OrderLevel* levelsDev = reinterpret_cast<OrderLevel*>(colsDev + cols.size());
+    HIP_OK(hipMemcpyAsync(ecolsDev, ecols.data(), ecols.size() * sizeof(OrderEmitCol), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(colsDev, cols.data(), cols.size() * sizeof(GroupCol), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(levelsDev, levels.data(), levels.size() * sizeof(OrderLevel), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vectors are pageable: copied before they go
+
+    // ---- select: the rows of the K first places, in no order
+    OrderEmitArgs ea{};
+    ea.n = n;
+    ea.ncols = ncols;
+    ea.cols = ecolsDev;
+    if (select) {
+        OrderArgs oa{};
+        oa.n = n;
+        oa.cols = colsDev;
+        oa.levels = levelsDev;
+        oa.nlevels = static_cast<int32_t>(levels.size());
+        oa.mark = c->obMark.get<uint8_t>(n);
+        oa.listCap = n / kOrderCompactDiv + 1;
+        oa.list[0] = c->obList[0].get<uint32_t>(oa.listCap);
+        oa.list[1] = c->obList[1].get<uint32_t>(oa.listCap);
+        oa.hist = c->obHist.get<uint64_t>(256);
+        oa.S = c->obState.get<OrderState>(1);
+        oa.win = c->obWin.get<uint32_t>(K);
+        oa.winCap = K;
+        OrderState st{};
+        st.rank = K - 1;
+        st.nTied = n;
+        HIP_OK(hipMemsetAsync(oa.mark, kOrdTied, n, c->stream));
+        HIP_OK(hipMemsetAsync(oa.hist, 0, 256 * sizeof(uint64_t), c->stream));
+        HIP_OK(hipMemcpyAsync(oa.S, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));                  // st is on the stack
+        uint64_t bytes = 0;
+        for (const OrderLevel& L : levels) bytes += n * static_cast<uint64_t>(L.bits / 8 + 1);   // upper bound: every step over all rows
+        c->timed("order_select", bytes, [&] {
+            for (size_t l = 0; l < levels.size(); l++) {
+                for (int shift = levels[l].bits - 8; shift >= 0; shift -= 8)
+                    if (launchOrderStep(oa, static_cast<int>(l), shift, l + 1 == levels.size() && shift == 0, c->stream))
+                        throw Error{NGX_E_DEVICE, "order step"};
+                HIP_OK(hipMemcpyAsync(&st, oa.S, sizeof st, hipMemcpyDeviceToHost, c->stream));   // once per level, not per digit
+                HIP_OK(hipStreamSynchronize(c->stream));
+                if (st.err) throw Error{NGX_E_DEVICE, "order by: inconsistent counts"};
+                if (st.done) break;
+            }
+            if (launchOrderGather(oa, c->stream)) throw Error{NGX_E_DEVICE, "order gather"};
+        });
+        HIP_OK(hipMemcpyAsync(&st, oa.S, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (st.err || !st.done || st.nWin != K) throw Error{NGX_E_DEVICE, "order by: winner count out of range"};
+        ea.rows = oa.win;
+        ea.m = K;
+    } else if (levels.size() == 1) {                              // LIMIT alone, or only constant factors: rows as stored
+        ea.base = offset;
+        ea.m = std::min(K, n) - offset;
+    } else {                                                      // K >= n: every row, ordered below
+        ea.m = n;
+    }
+    const uint64_t m = ea.m;
+
+    // ---- emit
+    ea.cells = c->obCells.get<GroupCell>(m * ncols);
+    uint64_t strBytes = 0;
+    if (anyString) {
+        uint64_t* slen = c->obSlen.get<uint64_t>(m + 1);
+        uint64_t* spre = c->obSpre.get<uint64_t>(m + 1);
+        uint64_t* tiles = c->obTiles.get<uint64_t>((m + kTile - 1) / kTile + 1);
+        if (launchOrderStrLen(ea, slen, c->stream)) throw Error{NGX_E_DEVICE, "order string lengths"};
+        if (launchScanU64(slen, m, spre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "order string scan"};
+        strBytes = readScalar(c, spre + m);
+        ea.strPre = spre;
+        ea.strOut = c->obStr.get<char>(std::max<uint64_t>(strBytes, 1));
+    }
+    c->timed("order_emit", m * ncols * sizeof(GroupCell) + strBytes, [&] {
+        if (launchOrderEmit(ea, c->stream)) throw Error{NGX_E_DEVICE, "order emit"};
+    });
+    HIP_OK(hipEventRecord(ev1, c->stream));
+    std::vector<ngx_cell> cells(m * ncols);
+    std::vector<uint32_t> rows(m);
+    HIP_OK(hipMemcpyAsync(cells.data(), ea.cells, cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
+    if (ea.rows) HIP_OK(hipMemcpyAsync(rows.data(), ea.rows, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    R.strings.resize(strBytes);
+    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], ea.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+    c->collectTimings();
+    R.r.device_ms = ms;
+
+    // ---- the winners in order (factors, then the row index), less the first `offset`
+    const auto t0 = std::chrono::steady_clock::now();
+    if (levels.size() == 1) {
+        R.cells = std::move(cells);
+    } else {
+        if (!ea.rows)
+            for (uint64_t i = 0; i < m; i++) rows[i] = static_cast<uint32_t>(i);
+        std::vector<uint32_t> perm(m);
+        for (uint64_t i = 0; i < m; i++) perm[i] = static_cast<uint32_t>(i);
+        const char* sbase = R.strings.data();
+        auto less = [&](uint32_t a, uint32_t b) {
+            for (int32_t f = 0; f < op->nfactors; f++) {
+                const int32_t y = op->factors[f].col, t = r->col_types[y];
+                const ngx_cell* x = &cells[static_cast<uint64_t>(a) * ncols + y];
+                const ngx_cell* z = &cells[static_cast<uint64_t>(b) * ncols + y];
+                if (op->factors[f].desc) std::swap(x, z);
+                if (t == NGX_T_STRING) {
+                    const size_t common = static_cast<size_t>(std::min(x->str_len, z->str_len));
+                    const int cmp = common ? std::memcmp(sbase + x->v.str_off, sbase + z->v.str_off, common) : 0;
+                    if (cmp) return cmp < 0;
+                    if (x->str_len != z->str_len) return x->str_len < z->str_len;
+                } else if (t == NGX_T_DOUBLE || t == NGX_T_FLOAT) {
+                    const uint64_t kx = orderDoubleKey(x->v.i), kz = orderDoubleKey(z->v.i);
+                    if (kx != kz) return kx < kz;
+                } else if (x->v.i != z->v.i) {
+                    return x->v.i < z->v.i;
+                }
+            }
+            return rows[a] < rows[b];
+        };
+        std::sort(perm.begin(), perm.end(), less);
+        const uint64_t keep = m > offset ? m - offset : 0;
+        R.cells.resize(keep * ncols);
+        for (uint64_t i = 0; i < keep; i++)
+            std::memcpy(&R.cells[i * ncols], &cells[static_cast<uint64_t>(perm[offset + i]) * ncols], ncols * sizeof(ngx_cell));
+    }
+    R.r.host_sort_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    R.r.nrows = ncols ? R.cells.size() / ncols : 0;
+    R.r.cells = R.cells.data();
+    R.r.strings = R.strings.data();
+    R.r.strings_len = strBytes;
+    c->orderByDevice++;
+    return NGX_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t ngx_go_order_by(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* plan, ngx_order_result** out) {
+    if (!c || !r || !plan || !out) return NGX_E_BAD_ARGUMENT;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto R = std::make_unique<OrderResultHolder>();
+    int32_t rc;
+    try {
+        rc = orderBy(c, r, plan, *R);
+    } catch (const Error& e) {
+        (void)hipStreamSynchronize(c->stream);                    // no kernel left reading the descriptors
+        rc = fail(c, e.code, e.msg);
+    }
+    R->r.code = rc;
+    *out = &R.release()->r;
+    return rc;
+}
+
+extern "C" void ngx_order_result_free(ngx_order_result* r) {
+    if (r) delete reinterpret_cast<OrderResultHolder*>(r);
 }

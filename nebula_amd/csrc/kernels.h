@@ -432,6 +432,85 @@ struct GroupEmitArgs {
 };
 int launchGroupStrLen(const GroupEmitArgs& a, uint64_t* slen, hipStream_t s);
 int launchGroupEmit(const GroupEmitArgs& a, hipStream_t s);
+// ORDER BY ... LIMIT over a device-resident result (orderby.hip; ngx_go_order_by): the K first rows of the
+// order are selected by an MSD radix select over levels. A level is one order-preserving unsigned word per
+// row of `bits` significant bits (a multiple of 8), consumed 8 bits a step from the top:
+//   kOrdInt     the value sign-extended from its stored width plus 2^(bits - 1): bits = 8 * stored width
+//   kOrdDouble  the bits with -0.0 read as +0.0, then all flipped for a negative value, else the sign bit
+//               (a NaN is placed by its bits)
+//   kOrdStrWord bytes [8 * word, 8 * word + 8) of the string, big-endian, zero-padded
+//   kOrdStrLen  the string's length (after its ceil(maxlen / 8) words: a proper prefix orders first)
+//   kOrdRow     the row's index in the result, always ascending: the last level, which makes the order total
+// desc complements the word within its bits.
+constexpr int kOrderMaxFactors = 8;
+constexpr uint32_t kOrderMaxStr = 256;              // bytes of the longest string a factor column may hold
+constexpr uint32_t kOrderCompactDiv = 16;           // the tied rows are listed once they are <= 1 / 16 of the rows read
+constexpr uint32_t kOrderAppendBuf = 2048;          // row ids a workgroup collects in LDS before it reserves list space
+enum { kOrdInt = 0, kOrdDouble, kOrdStrWord, kOrdStrLen, kOrdRow };
+enum { kOrdTied = 0, kOrdWin = 1, kOrdOut = 2 };   // a row's mark
+struct OrderLevel {
+    int32_t col;                        // index into OrderArgs::cols
+    int32_t kind;                       // kOrd*
+    int32_t word;                       // kOrdStrWord: which 8 bytes
+    int32_t desc;
+    int32_t bits;
+    int32_t pad;
+};
+// the selection's state, one copy in device memory. The pivot is the row of 0-based rank `rank` among the
+// tied rows; rows below it win, rows above it are out. k_order_pick is the only writer of every field but
+// the append counters (fill, nWin: one atomicAdd per LDS buffer flush) and err.
+struct OrderState {
+    uint64_t rank;
+    uint64_t nTied;
+    uint64_t listLen;                   // listed: entries of list[cur]
+    uint64_t fill;                      // entries appended to list[cur ^ 1] by the running compaction
+    uint64_t nWin;                      // entries appended to the winners
+    uint32_t hasPrev, pLevel, pShift, pDigit;   // the digit decided last: rows marked lazily by the next pass
+    uint32_t listed;                    // 0: the tied rows are the rows marked kOrdTied among all n; 1: list[cur] holds them
+    uint32_t cur;
+    uint32_t compacted;                 // the compaction after the last pick listed the tied rows in list[cur ^ 1]
+    uint32_t done;                      // the pivot is known: no more counting
+    uint32_t err;                       // a count that cannot be (no bucket holds the rank, a list past its capacity)
+    uint32_t pad;
+};
+struct OrderArgs {
+    uint64_t n;
+    const GroupCol* cols;               // device arrays
+    const OrderLevel* levels;
+    int32_t nlevels;
+    uint8_t* mark;                      // n marks, kOrdTied at the start
+    uint32_t* list[2];                  // listCap row ids each
+    uint64_t listCap;
+    uint64_t* hist;                     // 256 words, zero between steps (k_order_pick clears what it read)
+    OrderState* S;
+    uint32_t* win;                      // winCap winners' rows
+    uint64_t winCap;
+};
+// max over len[0 .. n) into *out (zeroed by the launcher)
+int launchOrderMaxLen(const uint32_t* len, uint64_t n, uint32_t* out, hipStream_t s);
+// one step: count the tied rows' digit (level, shift) per workgroup in LDS, one flush each; pick the digit
+// holding the rank; list the tied rows if they became few. Nothing runs once S->done is set.
+int launchOrderStep(const OrderArgs& a, int level, int shift, bool last, hipStream_t s);
+// after the last step: win[0 .. S->nWin) = the rows below the pivot and the pivot, in no order
+int launchOrderGather(const OrderArgs& a, hipStream_t s);
+// the rows' cells (as k_group_emit): every column of rows[i] (rows null: row base + i), i < m
+struct OrderEmitCol {
+    GroupCol c;
+    const uint8_t* type;                // per-row value types of an UNKNOWN-typed column, else null
+    int32_t cell;                       // NGX_CELL_* of a statically typed column
+    int32_t pad;
+};
+struct OrderEmitArgs {
+    uint64_t n, m, base;
+    const uint32_t* rows;
+    int32_t ncols;
+    const OrderEmitCol* cols;           // device array
+    const uint64_t* strPre;             // exclusive scan of launchOrderStrLen's lengths; null: no string cells
+    char* strOut;
+    GroupCell* cells;                   // m * ncols
+};
+int launchOrderStrLen(const OrderEmitArgs& a, uint64_t* slen, hipStream_t s);
+int launchOrderEmit(const OrderEmitArgs& a, hipStream_t s);
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

@@ -182,6 +182,29 @@ class GroupBySpec:
     yields: List[Tuple[str, int, object]]
 
 
+class OrderFactorC(ctypes.Structure):
+    _fields_ = [("col", c_i32), ("desc", c_i32)]
+
+
+class OrderPlanC(ctypes.Structure):
+    _fields_ = [("nfactors", c_i32), ("factors", P(OrderFactorC)), ("offset", c_i64), ("count", c_i64)]
+
+
+class OrderResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("nrows", c_u64), ("cells", P(Cell)),
+                ("strings", ctypes.c_void_p), ("strings_len", c_u64), ("input_rows", c_u64), ("device_ms", c_dbl),
+                ("host_sort_ms", c_dbl)]
+
+
+@dataclass
+class OrderBySpec:
+    """ngx_order_plan: (GO YIELD column, descending) per ORDER BY factor (none: LIMIT alone), and the LIMIT's
+    offset and count (count < 0: no LIMIT, which the library refuses)."""
+    factors: List[Tuple[int, bool]]
+    offset: int = 0
+    count: int = -1
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -214,6 +237,8 @@ SIGNATURES = {
     "ngx_go_result_digest": (c_i32, [ctypes.c_void_p, P(GoResultC), P(c_u64)]),
     "ngx_go_group_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GroupPlanC), P(P(GroupResultC))]),
     "ngx_group_result_free": (None, [P(GroupResultC)]),
+    "ngx_go_order_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(OrderPlanC), P(P(OrderResultC))]),
+    "ngx_order_result_free": (None, [P(OrderResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
     "ngx_kernel_stats": (c_i32, [ctypes.c_void_p, P(P(KernelStat)), P(c_i32)]),
     "ngx_set_flag": (c_i32, [ctypes.c_void_p, ctypes.c_char_p, c_i64]),
@@ -340,6 +365,9 @@ class GoResult:
     go_device_ms: float = 0.0
     go_nrows: int = 0
     group_device_ms: float = 0.0
+    # order_by: the selection's device time and the library's host sort of the winners (go_* as for group_by)
+    order_device_ms: float = 0.0
+    order_host_sort_ms: float = 0.0
 
 
 @dataclass
@@ -379,6 +407,7 @@ class PreparedGo:
 
 class Engine:
     device_group_by = True                     # go(..., group_by=...) groups a device-resident result (pipeline.py)
+    device_order_by = True                     # go(..., order_by=...) selects a device-resident result's top rows
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -531,7 +560,7 @@ class Engine:
            raise_on_error: bool = False, rows: bool = True, on_device: bool = False, fetch: bool = False,
            columnar: bool = False, digest_fn=None, arrays: bool = True, input=None,
            yield_only: bool = False, compact: bool = False, device_digest: bool = False,
-           group_by: Optional[GroupBySpec] = None) -> GoResult:
+           group_by: Optional[GroupBySpec] = None, order_by: Optional[OrderBySpec] = None) -> GoResult:
         """Run one GO. rows=False skips decoding cells into Python tuples; on_device=True leaves the
         result rows in HBM (GoResult.nrows and the statistics only); with fetch=True the HBM arrays
         (src/dst/rank/type and the columnar YIELD columns) are copied back into the result.
@@ -548,8 +577,11 @@ class Engine:
         group_by: the GO runs with on_device and its rows are grouped in HBM (ngx_go_group_by) before the
         result is freed; GoResult.rows / col_types / nrows are then the group rows, device_ms the grouping's
         and group_device_ms too (go_device_ms keeps the traversal's). NGX_E_UNSUPPORTED comes back as a
-        result with that code and the reason (the caller groups on the host), not as an exception."""
-        if group_by is not None:
+        result with that code and the reason (the caller groups on the host), not as an exception.
+        order_by: likewise, rows [offset, offset + count) of the result ordered by the spec's factors are
+        selected in HBM (ngx_go_order_by); GoResult.rows / nrows are those rows in order, col_types the GO's,
+        device_ms / order_device_ms the selection's, order_host_sort_ms the library's sort of the winners."""
+        if group_by is not None or order_by is not None:
             on_device, columnar = True, False
         if isinstance(s, PreparedGo):                       # its own pushdown / result-placement flags
             plan, keep = s.plan, s
@@ -587,6 +619,8 @@ class Engine:
                     res.dev_consts = (r.dev_key_const[:3], r.dev_col_const[:nc] if nc and r.dev_col_const else [0] * nc)
                 if group_by is not None and rc == 0:
                     self._group_by(out, group_by, res)
+                elif order_by is not None and rc == 0:
+                    self._order_by(out, order_by, res)
                 if device_digest and rc == 0:
                     d3 = (c_u64 * 3)()
                     drc = self.L.ngx_go_result_digest(self.h, out, d3)
@@ -665,6 +699,31 @@ class Engine:
             res.device_ms = res.group_device_ms = g.device_ms
         finally:
             self.L.ngx_group_result_free(gout)
+
+    def _order_by(self, go_out, spec: OrderBySpec, res: GoResult):
+        fs = (OrderFactorC * max(1, len(spec.factors)))()
+        for i, (col, desc) in enumerate(spec.factors):
+            fs[i].col, fs[i].desc = col, 1 if desc else 0
+        plan = OrderPlanC(len(spec.factors), fs, spec.offset, spec.count)
+        oout = P(OrderResultC)()
+        rc = self.L.ngx_go_order_by(self.h, go_out, ctypes.byref(plan), ctypes.byref(oout))
+        try:
+            res.go_device_ms, res.go_nrows = res.device_ms, res.nrows
+            if rc:
+                err = self.L.ngx_last_error(self.h).decode()
+                if rc != E_UNSUPPORTED:
+                    raise EngineError(rc, err)
+                res.ok, res.code, res.error = False, rc, err
+                return
+            o = oout.contents
+            strings = ctypes.string_at(o.strings, o.strings_len) if o.strings_len else b""
+            res.rows = _cells(o.cells, o.nrows, o.ncols, strings)
+            res.col_types = o.col_types[:o.ncols] if o.ncols else []
+            res.nrows = o.nrows
+            res.device_ms = res.order_device_ms = o.device_ms
+            res.order_host_sort_ms = o.host_sort_ms
+        finally:
+            self.L.ngx_order_result_free(oout)
 
     def go_batch(self, prepared: Sequence["PreparedGo"], digests: bool = False):
         """Run prepared GO plans back to back in one native call (ngx_go_batch): per query (code, result

@@ -646,3 +646,82 @@ def parse_group_by(src: str) -> GroupBySentence:
         s.yields = _agg_columns(p)
     p.expect("eof")
     return s
+
+
+# ------------------------------------------------------------------------------ ORDER BY / LIMIT sentences
+@dataclass
+class OrderBySentence:
+    """Parsed `ORDER BY <factor>[, <factor>...]` (order_by_sentence, parser.yy:819-859): (input column
+    name, descending) per factor. A factor is `$-.col` or a bare label, then ASC (the default) or DESC."""
+    factors: List[Tuple[str, bool]] = field(default_factory=list)
+
+
+@dataclass
+class LimitSentence:
+    """Parsed `LIMIT n` / `LIMIT off, n` / `LIMIT a OFFSET b` (limit_sentence, parser.yy:996-1011). The
+    grammar builds LimitSentence($2, $4) for the OFFSET form too: a is the offset and b the count."""
+    offset: int = 0
+    count: int = 0
+
+
+def is_order_by(src: str) -> bool:
+    return re.match(r"\s*ORDER\s+BY\b", src, re.I) is not None
+
+
+def is_limit(src: str) -> bool:
+    return re.match(r"\s*LIMIT\b", src, re.I) is not None
+
+
+def _word(p: Parser, *words: str) -> Optional[str]:
+    t = p.peek()
+    if t.kind == "name" and t.text.upper() in words:
+        p.take()
+        return t.text.upper()
+    return None
+
+
+def parse_order_by(src: str) -> OrderBySentence:
+    p = Parser(src)
+    for word in ("ORDER", "BY"):
+        if _word(p, word) is None:
+            raise SyntaxError(f"expected {word}, got {p.peek().text!r}")
+    s = OrderBySentence()
+    while True:
+        t = p.peek()
+        if t.kind == "ref" and t.text == "$-":                    # input_ref_expression (parser.yy:384-395)
+            p.take()
+            if p.accept("op", "."):
+                col = "*" if p.accept("op", "*") else p.label()
+            else:
+                col = "id"
+        elif t.kind == "name" and t.text.upper() not in ("ASC", "DESC"):
+            col = p.take().text                                   # LABEL
+        else:
+            raise SyntaxError(f"expected an order factor, got {t.text!r}")
+        s.factors.append((col, _word(p, "ASC", "DESC") == "DESC"))
+        if not p.accept("op", ","):
+            break
+    p.expect("eof")
+    return s
+
+
+def parse_limit(src: str) -> LimitSentence:
+    p = Parser(src)
+    if _word(p, "LIMIT") is None:
+        raise SyntaxError(f"expected LIMIT, got {p.peek().text!r}")
+
+    def integer() -> int:                                         # INTEGER: no sign in the grammar
+        t = p.peek()
+        if t.kind not in ("int", "hex"):
+            raise SyntaxError(f"expected an integer, got {t.text!r}")
+        p.take()
+        v = int(t.text, 0)
+        if v > (1 << 63) - 1:
+            raise SyntaxError("integer out of range")
+        return v
+    a = integer()
+    s = LimitSentence(0, a)
+    if p.accept("op", ",") or _word(p, "OFFSET") is not None:
+        s = LimitSentence(a, integer())
+    p.expect("eof")
+    return s

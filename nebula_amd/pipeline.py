@@ -13,7 +13,11 @@ library, include/nebula_gn.h ngx_go with input_* set):
     every input column.
   - GroupByExecutor (src/graph/GroupByExecutor.cpp): `... | GROUP BY <cols> YIELD <aggregates>` over the
     left side's interim result (nebula_amd/groupby.py).
-GO and GROUP BY are the traversal sentences here (ORDER BY, LIMIT and `| YIELD` are outside this path).
+  - OrderByExecutor / LimitExecutor (src/graph/OrderByExecutor.cpp, LimitExecutor.cpp): `... | ORDER BY
+    <factors>` and `... | LIMIT [off,] n` over the left side's interim result (nebula_amd/orderby.py), when
+    the caller opts in with order_limit=True.
+GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
+default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
 """
 from __future__ import annotations
@@ -21,7 +25,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-from . import groupby, ngql
+from . import groupby, ngql, orderby
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
 _KIND_TYPE = {"bool": T_BOOL, "int": T_INT, "id": T_INT, "timestamp": T_INT, "float": T_DOUBLE,
@@ -127,9 +131,15 @@ class Outcome:
 class Pipeline:
     """Runs nGQL text made of GO sentences, pipes, parentheses, `$v = ...' and `;'."""
 
-    def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True, **go_kw):
-        """device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device."""
+    def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
+                 order_limit: bool = False, device_order_by: bool = True, **go_kw):
+        """device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device.
+        order_limit=True: ORDER BY and LIMIT sentences run (off by default: they are refused like every
+        sentence outside this path); device_order_by=False: `GO | ORDER BY | LIMIT` and `GO | LIMIT` order
+        and cut on the host even where the backend could select the rows on the device."""
         self.device_group_by = device_group_by
+        self.order_limit = order_limit
+        self.device_order_by = device_order_by
         self.backend = backend
         self.space = space
         self.edge_names = list(edge_names)
@@ -268,23 +278,117 @@ class Pipeline:
             return Outcome(False, str(e), s.column_names())
         return Outcome(True, "", names, types, rows)
 
+    def _order_spec(self, go_text: str, ob_text: Optional[str], lim_text: str):
+        """(GoSentence, spec) when `GO | ORDER BY | LIMIT` (ob_text None: `GO | LIMIT`) can select its rows on
+        the device (ngx_go_order_by): a plain GO as in _device_spec, factors that are its columns. None: the
+        host path decides (and reports any error)."""
+        from .engine import OrderBySpec
+        try:
+            s, lim = ngql.parse_go(go_text), ngql.parse_limit(lim_text)
+            names = s.column_names(self.edge_names)
+            if s.from_type or s.distinct or not s.yields or len(set(names)) != len(names):
+                return None
+            for y in s.yields:
+                if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
+                        any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
+                    return None
+            factors = []
+            if ob_text is not None:
+                for col, desc in ngql.parse_order_by(ob_text).factors:
+                    if col not in names:
+                        return None
+                    factors.append((names.index(col), desc))
+            return s, OrderBySpec(factors, lim.offset, lim.count)
+        except (SyntaxError, ValueError):
+            return None
+
+    def _go_order_by(self, go_text: str, ob_text: Optional[str], lim_text: str) -> Optional[Outcome]:
+        """`GO | [ORDER BY |] LIMIT` with the selection on the device; None when the host path has to run."""
+        plan = self._order_spec(go_text, ob_text, lim_text)
+        if plan is None:
+            return None
+        s, spec = plan
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            r = self.backend.go(self.space, s, order_by=spec, yield_only=True, compact=True, **kw)
+        except RuntimeError as e:
+            if getattr(e, "code", 0) == -1002:                    # the device-resident GO itself: the plain path decides
+                return None
+            raise
+        names = s.column_names(self.edge_names)
+        if not r.ok:
+            if r.code == -1002:                                   # NGX_E_UNSUPPORTED: order and cut on the host
+                return None
+            return Outcome(False, r.error, names)
+        # the interim schema the host path would hand on: UNKNOWN columns take the first row's type
+        return Outcome(True, "", names, Interim.from_result(names, r.col_types, r.rows).types, list(r.rows))
+
+    def _order_by(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """An ORDER BY sentence on the pipe's input: OrderByExecutor restated on the host (orderby.order_by)."""
+        try:
+            s = ngql.parse_order_by(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        try:
+            names, types, rows = orderby.order_by(s, *((inp.names, inp.types, inp.rows) if inp is not None else (None, [], [])))
+        except orderby.OrderByError as e:
+            return Outcome(False, str(e), list(inp.names) if inp is not None else [])
+        return Outcome(True, "", names, types, rows)
+
+    def _limit(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """A LIMIT sentence on the pipe's input: LimitExecutor restated on the host (orderby.limit)."""
+        try:
+            s = ngql.parse_limit(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        try:
+            names, types, rows = orderby.limit(s, *((inp.names, inp.types, inp.rows) if inp is not None else (None, [], [])))
+        except orderby.OrderByError as e:
+            return Outcome(False, str(e), list(inp.names) if inp is not None else [])
+        return Outcome(True, "", names, types, rows)
+
     def _piped(self, text: str, inp: Optional[Interim]) -> Outcome:
         parts = _split(text, "|")
+        if self.order_limit:                                      # the reference parses the whole text first
+            for part in parts:
+                body = _unwrap(part)
+                if len(_split(body, "|")) > 1:                    # ( piped ): checked when it runs
+                    continue
+                try:
+                    if ngql.is_order_by(body):
+                        ngql.parse_order_by(body)
+                    elif ngql.is_limit(body):
+                        ngql.parse_limit(body)
+                except (SyntaxError, ValueError) as e:
+                    return Outcome(False, "SyntaxError: %s" % e)
         cur = inp
         out = None
-        skip = False
+        skip = 0
         for i, part in enumerate(parts):
             body = _unwrap(part)
-            if skip:                                              # grouped on the device with the GO before it
-                skip = False
-                if i + 1 < len(parts):
+            if skip:                                              # ran on the device with the GO before it
+                skip -= 1
+                if not skip and i + 1 < len(parts):
                     cur = Interim.from_result(out.names, out.col_types, out.rows)
                 continue
+            if self.order_limit and self.device_order_by and getattr(self.backend, "device_order_by", False) \
+                    and i + 1 < len(parts) and body.upper().startswith("GO"):
+                nxt = [_unwrap(p) for p in parts[i + 1:i + 3]]
+                dev, took = None, 0
+                if ngql.is_limit(nxt[0]):
+                    dev, took = self._go_order_by(body, None, nxt[0]), 1
+                elif len(nxt) == 2 and ngql.is_order_by(nxt[0]) and ngql.is_limit(nxt[1]):
+                    dev, took = self._go_order_by(body, nxt[0], nxt[1]), 2
+                if dev is not None:
+                    out, skip = dev, took
+                    if not out.ok:
+                        return out
+                    continue
             if self.device_group_by and getattr(self.backend, "device_group_by", False) and i + 1 < len(parts) \
                     and body.upper().startswith("GO") and ngql.is_group_by(_unwrap(parts[i + 1])):
                 dev = self._go_group_by(body, _unwrap(parts[i + 1]))
                 if dev is not None:
-                    out, skip = dev, True
+                    out, skip = dev, 1
                     if not out.ok:
                         return out
                     continue
@@ -294,6 +398,10 @@ class Pipeline:
                 out = self._yield_constant(body)
             elif ngql.is_group_by(body):
                 out = self._group_by(body, cur)
+            elif self.order_limit and ngql.is_order_by(body):
+                out = self._order_by(body, cur)
+            elif self.order_limit and ngql.is_limit(body):
+                out = self._limit(body, cur)
             else:
                 if not body.upper().startswith("GO"):
                     raise PipelineError("only GO sentences run in this path: " + body[:40])
@@ -323,5 +431,7 @@ class Pipeline:
         return out
 
 
-def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True, **go_kw) -> Outcome:
-    return Pipeline(backend, space, edge_names, device_group_by=device_group_by, **go_kw).run(text)
+def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
+        order_limit: bool = False, device_order_by: bool = True, **go_kw) -> Outcome:
+    return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
+                    device_order_by=device_order_by, **go_kw).run(text)
