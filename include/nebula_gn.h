@@ -424,7 +424,9 @@ int32_t ngx_go_result_digest(ngx_ctx* ctx, const ngx_go_result* r, uint64_t out[
  * bit-reproducible. Output types are those of the result cells; the order of the group rows is not fixed.
  * Flags: "group_by_device" counts the calls completed on the device, "group_by_lds" those whose
  * accumulation ran per workgroup in LDS; "group_lds_max" (-1: by size) is the largest number of groups
- * that takes the LDS path, 0 forces global atomics. */
+ * that takes the LDS path, 0 forces global atomics; "group_grid_max" (0, the default: built-in, else 1 .. 1024)
+ * caps the workgroups of both accumulation kernels (built-in: 1024 on the LDS path), so a test can make one
+ * workgroup sweep every row. Same results under every setting. */
 #define NGX_AGG_GROUP 0                /* no function: a key column or a constant */
 #define NGX_AGG_COUNT 1
 #define NGX_AGG_COUNT_DISTINCT 2
@@ -482,7 +484,13 @@ void ngx_group_result_free(ngx_group_result* r);
  * (per-row) type, more than 8 factors, a factor string longer than 256 bytes, world > 1 (the shards'
  * winners are not merged yet). The caller then orders on the host. A count of 0 or an offset at or past the
  * end answers with no rows and launches nothing.
- * Flags: "order_by_device" counts the calls completed on the device; "order_k_max" is settable. */
+ * Flags: "order_by_device" counts the calls completed on the device; "order_k_max" is settable;
+ * "order_grid_max" (0, the default: built-in 2048, else 1 .. 2048) caps the workgroups of the count, listing
+ * and gather kernels (256 rows a workgroup and sweep). Same results under every setting. Read-only, summed over
+ * the context's calls, for tests that must know which path ran: "order_compactions" (steps that read a freshly
+ * listed set of tied rows), "order_list_compactions" (those listed from a list, not from all rows),
+ * "order_loop_flushes" (a workgroup's LDS row-id buffer emptied inside its sweep loop, in a listing or the
+ * gather: it kept more than 1792 rows). */
 typedef struct {
     int32_t col;                       /* GO YIELD column */
     int32_t desc;                      /* 0 ASC, 1 DESC */

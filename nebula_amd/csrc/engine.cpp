@@ -236,11 +236,15 @@ struct ngx_ctx {
     hipEvent_t gbEv[2] = {nullptr, nullptr};            // ngx_group_result / ngx_order_result.device_ms: made on the first call, kept
     uint64_t groupByDevice = 0, groupByLds = 0;        // calls completed on the device / through the LDS path
     int64_t groupLdsMax = -1;                           // flag group_lds_max: -1 by size, else the largest group count
+    uint32_t groupGridMax = 0;                          // flag group_grid_max: most accumulation workgroups, 0: built-in
     // ngx_go_order_by: row marks, the two tied-row lists, digit counters, state, descriptors, string-length maxima,
     // winners' rows, their string lengths and scan, output cells and string bytes, scan tiles
     DBuf obMark, obList[2], obHist, obState, obDesc, obMax, obWin, obSlen, obSpre, obCells, obStr, obTiles;
     uint64_t orderByDevice = 0;                         // calls completed on the device (flag order_by_device)
     int64_t orderKMax = 65536;                          // flag order_k_max: the largest offset + count selected on the device
+    uint32_t orderGridMax = 0;                          // flag order_grid_max: most workgroups of a sweep, 0: built-in
+    // paths the selections took so far (OrderState's counters summed; flags order_compactions, ...)
+    uint64_t orderCompactions = 0, orderListCompactions = 0, orderLoopFlushes = 0;
     DBuf localBits, pullGather;                         // world > 1 pull: this shard's frontier bitmap, all shards' 
     struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
     std::vector<ngx_stat> statList;                     // ngx_stats view
@@ -2128,6 +2132,18 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
     }
     if (n == "jit_wait") { c->jit.drain(); return NGX_OK; }
     if (n == "group_lds_max") { c->groupLdsMax = value < 0 ? -1 : value; return NGX_OK; }
+    if (n == "group_grid_max") {
+        if (value < 0 || value > static_cast<int64_t>(kGroupLdsGridMax))
+            return fail(c, NGX_E_BAD_ARGUMENT, "group_grid_max: 0 (built-in) or 1 .. " + std::to_string(kGroupLdsGridMax));
+        c->groupGridMax = static_cast<uint32_t>(value);
+        return NGX_OK;
+    }
+    if (n == "order_grid_max") {
+        if (value < 0 || value > static_cast<int64_t>(kOrderGridMax))
+            return fail(c, NGX_E_BAD_ARGUMENT, "order_grid_max: 0 (built-in) or 1 .. " + std::to_string(kOrderGridMax));
+        c->orderGridMax = static_cast<uint32_t>(value);
+        return NGX_OK;
+    }
     if (n == "order_k_max") {
         if (value < 1 || value > (int64_t(1) << 24)) return fail(c, NGX_E_BAD_ARGUMENT, "order_k_max: 1 .. 2^24");
         c->orderKMax = value;
@@ -2187,6 +2203,11 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "group_lds_max") *value = c->groupLdsMax;
     else if (n == "order_by_device") *value = static_cast<int64_t>(c->orderByDevice);
     else if (n == "order_k_max") *value = c->orderKMax;
+    else if (n == "group_grid_max") *value = c->groupGridMax;
+    else if (n == "order_grid_max") *value = c->orderGridMax;
+    else if (n == "order_compactions") *value = static_cast<int64_t>(c->orderCompactions);
+    else if (n == "order_list_compactions") *value = static_cast<int64_t>(c->orderListCompactions);
+    else if (n == "order_loop_flushes") *value = static_cast<int64_t>(c->orderLoopFlushes);
     else if (n == "jit_compiled") *value = static_cast<int64_t>(c->jit.compiled);
     else if (n == "jit_hits") *value = static_cast<int64_t>(c->jit.hits);
     else if (n == "jit_cached") *value = static_cast<int64_t>(c->jit.size());
@@ -5881,7 +5902,7 @@ int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, Gr
     const bool lds = !slots.empty() && stateBytes <= kGroupLdsBytes &&
                      (c->groupLdsMax < 0 ? stateBytes <= 32 * 1024 : ngroups <= static_cast<uint64_t>(c->groupLdsMax));
     c->timed(lds ? "group_accum_lds" : "group_accum", n * 8 * (slots.size() + 1), [&] {
-        if (launchGroupAccum(ga, lds, c->stream)) throw Error{NGX_E_DEVICE, "group accumulate"};
+        if (launchGroupAccum(ga, lds, c->groupGridMax, c->stream)) throw Error{NGX_E_DEVICE, "group accumulate"};
     });
 
     // ---- emit
@@ -6079,6 +6100,7 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
         oa.S = c->obState.get<OrderState>(1);
         oa.win = c->obWin.get<uint32_t>(K);
         oa.winCap = K;
+        oa.gridMax = c->orderGridMax;
         OrderState st{};
         st.rank = K - 1;
         st.nTied = n;
@@ -6102,6 +6124,9 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
         });
         HIP_OK(hipMemcpyAsync(&st, oa.S, sizeof st, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
+        c->orderCompactions += st.compactions;
+        c->orderListCompactions += st.listCompactions;
+        c->orderLoopFlushes += st.loopFlushes;
         if (st.err || !st.done || st.nWin != K) throw Error{NGX_E_DEVICE, "order by: winner count out of range"};
         ea.rows = oa.win;
         ea.m = K;

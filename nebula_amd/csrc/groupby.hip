@@ -235,7 +235,7 @@ int launchGroupAssign(const GroupAssignArgs& a, hipStream_t s) {
     return static_cast<int>(hipGetLastError());
 }
 
-int launchGroupAccum(const GroupAccumArgs& a, bool lds, hipStream_t s) {
+int launchGroupAccum(const GroupAccumArgs& a, bool lds, uint32_t gridMax, hipStream_t s) {
     if (a.ngroups == 0 || a.nslots == 0) return 0;
     const uint64_t words = a.ngroups * static_cast<uint64_t>(a.nslots);
     hipLaunchKernelGGL(k_group_init, dim3(static_cast<unsigned>((words + 255) / 256)), dim3(256), 0, s, a.slots, a.nslots,
@@ -244,10 +244,10 @@ int launchGroupAccum(const GroupAccumArgs& a, bool lds, hipStream_t s) {
     if (lds) {
         if (words * 8 > kGroupLdsBytes) return 1;
         // few groups: each workgroup folds many rows into its LDS copy before the one flush
-        const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((a.n + 255) / 256, 1024));
+        const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((a.n + 255) / 256, gridMax ? gridMax : kGroupLdsGridMax));
         hipLaunchKernelGGL(k_group_accum<true>, dim3(grid), dim3(256), words * 8, s, a);
     } else {
-        const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((a.n + 255) / 256, 1u << 20));
+        const unsigned grid = static_cast<unsigned>(std::min<uint64_t>((a.n + 255) / 256, gridMax ? gridMax : 1u << 20));
         hipLaunchKernelGGL(k_group_accum<false>, dim3(grid), dim3(256), 0, s, a);
     }
     return static_cast<int>(hipGetLastError());

@@ -362,6 +362,7 @@ int launchScatterKept(const ScatterArgs& a, hipStream_t s);
 // 8-byte device pointers with their lengths in len.
 constexpr int kGroupMaxKeys = 4;
 constexpr uint64_t kGroupLdsBytes = 64 * 1024;      // the LDS copy of the state one workgroup may hold
+constexpr uint32_t kGroupLdsGridMax = 1024;         // workgroups of the LDS accumulation (each flushes its copy once)
 enum { kGroupInt = 0, kGroupDouble = 1, kGroupString = 2 };
 struct GroupCol {
     const void* x;
@@ -402,8 +403,9 @@ struct GroupAccumArgs {
     const uint64_t* pre;                // exclusive scan of the leader flags: pre[leader row] = group id
     uint64_t* state;                    // nslots * ngroups words, initialised by the launcher
 };
-// lds: every workgroup aggregates into an LDS copy of the state (nslots * ngroups * 8 <= kGroupLdsBytes)
-int launchGroupAccum(const GroupAccumArgs& a, bool lds, hipStream_t s);
+// lds: every workgroup aggregates into an LDS copy of the state (nslots * ngroups * 8 <= kGroupLdsBytes).
+// gridMax (flag group_grid_max): most workgroups of either accumulation, 0: the built-in caps
+int launchGroupAccum(const GroupAccumArgs& a, bool lds, uint32_t gridMax, hipStream_t s);
 // one output cell per (group, yield column), laid out as ngx_cell
 struct GroupCell {
     int32_t kind;
@@ -446,6 +448,7 @@ constexpr int kOrderMaxFactors = 8;
 constexpr uint32_t kOrderMaxStr = 256;              // bytes of the longest string a factor column may hold
 constexpr uint32_t kOrderCompactDiv = 16;           // the tied rows are listed once they are <= 1 / 16 of the rows read
 constexpr uint32_t kOrderAppendBuf = 2048;          // row ids a workgroup collects in LDS before it reserves list space
+constexpr uint32_t kOrderGridMax = 2048;            // workgroups (of 256 rows a sweep) of the count / collect kernels
 enum { kOrdInt = 0, kOrdDouble, kOrdStrWord, kOrdStrLen, kOrdRow };
 enum { kOrdTied = 0, kOrdWin = 1, kOrdOut = 2 };   // a row's mark
 struct OrderLevel {
@@ -458,7 +461,7 @@ struct OrderLevel {
 };
 // the selection's state, one copy in device memory. The pivot is the row of 0-based rank `rank` among the
 // tied rows; rows below it win, rows above it are out. k_order_pick is the only writer of every field but
-// the append counters (fill, nWin: one atomicAdd per LDS buffer flush) and err.
+// the append counters (fill, nWin: one atomicAdd per LDS buffer flush), loopFlushes and err.
 struct OrderState {
     uint64_t rank;
     uint64_t nTied;
@@ -471,7 +474,10 @@ struct OrderState {
     uint32_t compacted;                 // the compaction after the last pick listed the tied rows in list[cur ^ 1]
     uint32_t done;                      // the pivot is known: no more counting
     uint32_t err;                       // a count that cannot be (no bucket holds the rank, a list past its capacity)
-    uint32_t pad;
+    // which paths the call took (flags order_compactions / order_list_compactions / order_loop_flushes)
+    uint32_t compactions;               // picks that read the counts of a freshly compacted list
+    uint32_t listCompactions;           // ... whose compaction read a list already (list -> list)
+    uint32_t loopFlushes;               // LDS buffer flushes inside a sweep loop of k_order_collect: one atomicAdd each
 };
 struct OrderArgs {
     uint64_t n;
@@ -485,6 +491,7 @@ struct OrderArgs {
     OrderState* S;
     uint32_t* win;                      // winCap winners' rows
     uint64_t winCap;
+    uint32_t gridMax;                   // most workgroups of a sweep (flag order_grid_max); 0: kOrderGridMax
 };
 // max over len[0 .. n) into *out (zeroed by the launcher)
 int launchOrderMaxLen(const uint32_t* len, uint64_t n, uint32_t* out, hipStream_t s);

@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void k_order_pick(OrderArgs a, uint32_t level,
     __syncthreads();
     if (threadIdx.x != 0) return;
     if (S->compacted) {                                           // the counts came from the new list: it is the current one now
+        S->compactions++;
+        if (S->listed) S->listCompactions++;                      // the compaction read a list already
         S->cur ^= 1;
         S->listed = 1;
         S->listLen = S->nTied;
@@ -236,7 +238,10 @@ __global__ __launch_bounds__(256) void k_order_collect(OrderArgs a) {
         __syncthreads();
         const uint32_t have = cnt;
         __syncthreads();                                          // everyone has read cnt before the next adds
-        if (have > kOrderAppendBuf - 256) flush(have);
+        if (have > kOrderAppendBuf - 256) {
+            flush(have);
+            if (threadIdx.x == 0) atomicAdd(&a.S->loopFlushes, 1u);
+        }
     }
     __syncthreads();
     const uint32_t have = cnt;
@@ -306,7 +311,9 @@ __global__ __launch_bounds__(256) void k_order_emit(OrderEmitArgs a) {
     }
 }
 
-unsigned orderGrid(uint64_t n) { return static_cast<unsigned>(std::min<uint64_t>((n + 255) / 256, 2048)); }
+unsigned orderGrid(uint64_t n, uint32_t gridMax = 0) {
+    return static_cast<unsigned>(std::min<uint64_t>((n + 255) / 256, gridMax ? gridMax : kOrderGridMax));
+}
 
 }  // namespace
 
@@ -319,16 +326,16 @@ int launchOrderMaxLen(const uint32_t* len, uint64_t n, uint32_t* out, hipStream_
 
 int launchOrderStep(const OrderArgs& a, int level, int shift, bool last, hipStream_t s) {
     if (a.n == 0 || a.n >= (1ULL << 32) || level < 0 || level >= a.nlevels || shift < 0 || shift > 56 || shift % 8) return 1;
-    hipLaunchKernelGGL(k_order_count, dim3(orderGrid(a.n)), dim3(256), 0, s, a, static_cast<uint32_t>(level), static_cast<uint32_t>(shift));
+    hipLaunchKernelGGL(k_order_count, dim3(orderGrid(a.n, a.gridMax)), dim3(256), 0, s, a, static_cast<uint32_t>(level), static_cast<uint32_t>(shift));
     hipLaunchKernelGGL(k_order_pick, dim3(1), dim3(256), 0, s, a, static_cast<uint32_t>(level), static_cast<uint32_t>(shift),
                        last ? 1u : 0u);
-    if (!last) hipLaunchKernelGGL(k_order_collect<false>, dim3(orderGrid(a.n)), dim3(256), 0, s, a);
+    if (!last) hipLaunchKernelGGL(k_order_collect<false>, dim3(orderGrid(a.n, a.gridMax)), dim3(256), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 
 int launchOrderGather(const OrderArgs& a, hipStream_t s) {
     if (a.n == 0 || a.n >= (1ULL << 32)) return 1;
-    hipLaunchKernelGGL(k_order_collect<true>, dim3(orderGrid(a.n)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_order_collect<true>, dim3(orderGrid(a.n, a.gridMax)), dim3(256), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 
