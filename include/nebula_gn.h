@@ -516,6 +516,37 @@ typedef struct {
 int32_t ngx_go_order_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_order_plan* plan, ngx_order_result** out);
 void ngx_order_result_free(ngx_order_result* r);
 
+/* ---------------------------------------------------------------- GROUP BY, then ORDER BY / LIMIT */
+/* `GO ... | GROUP BY <keys> YIELD <aggregates> | ORDER BY <factors> | LIMIT [off,] n` (and `GO ... | GROUP BY
+ * ... | LIMIT [off,] n`) with both sentences on the device: the grouping of ngx_go_group_by up to its state
+ * words, the group rows written as columns in HBM instead of cells (one array per yield column, indexed by the
+ * group's id), and the radix select of ngx_go_order_by over those columns. Only the cells and string bytes of
+ * the offset + count first groups of the order cross PCIe. `r` is a result_on_device result of this context,
+ * and the call comes before any other call on the context (as its two neighbours). `group` is read as
+ * ngx_go_group_by reads its plan; `order->factors[].col` names a yield column of `group` (0 .. nyields - 1).
+ * The answer is an ngx_order_result (ngx_order_result_free): ncols = group->nyields, col_types what
+ * ngx_go_group_by would report (0 when there are no groups), input_rows the number of groups, the rows the
+ * [offset, offset + count) window of the ordered group rows, their cells as ngx_go_group_by's (a COUNT is
+ * the same int64 whatever width the select read it at). device_ms runs from the table clear to the last cell.
+ * Order: as ngx_go_order_by compares, with the group's id as the last, ascending key. A group's id is the
+ * rank of its leader row (the row that claimed the group's slot in the key table) among the leaders, so it
+ * depends on which row won a race: groups equal on every factor come out in an order that is free, and may
+ * differ between two runs. That is one valid outcome of the reference, whose GroupByExecutor walks an
+ * unordered_map and whose OrderByExecutor sorts with std::sort. With no factors (LIMIT alone) the groups
+ * [offset, offset + count) by id come out, and nothing is launched after the column kernel but the emit.
+ * When offset + count reaches the number of groups every group row crosses and the library orders them.
+ * Eligibility is the conjunction of the two calls': NGX_E_UNSUPPORTED with ngx_go_group_by's reasons
+ * ("group by: ...": DOUBLE keys, STD, more than 4 keys, ... as listed there), checked first, then with
+ * ngx_go_order_by's ("order by: ...": count < 0, offset + count above "order_k_max", more than 8 factors, a
+ * factor string longer than 256 bytes; the last one is found after the grouping ran). A factor column outside
+ * the yields is NGX_E_BAD_ARGUMENT. A count of 0, an offset at or past the number of groups, or a result
+ * without rows answers with no rows.
+ * Flags: "group_order_device" (read-only) counts the calls completed on the device; "group_by_device" and
+ * "order_by_device" do not move. "group_by_lds" and the three "order_*" path counters rise as for the single
+ * calls; "group_lds_max", "group_grid_max", "order_grid_max" and "order_k_max" are obeyed. */
+int32_t ngx_go_group_order_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_group_plan* group,
+                              const ngx_order_plan* order, ngx_order_result** out);
+
 /* ---------------------------------------------------------------- measurement hooks */
 /* Per-kernel device times of the last ngx_go (HIP events on the engine stream), for bench.py. */
 typedef struct {

@@ -245,6 +245,9 @@ struct ngx_ctx {
     uint32_t orderGridMax = 0;                          // flag order_grid_max: most workgroups of a sweep, 0: built-in
     // paths the selections took so far (OrderState's counters summed; flags order_compactions, ...)
     uint64_t orderCompactions = 0, orderListCompactions = 0, orderLoopFlushes = 0;
+    // ngx_go_group_order_by: the group rows as columns (values, string lengths) and their descriptors
+    DBuf goCols, goLen, goDesc;
+    uint64_t groupOrderDevice = 0;                      // calls completed on the device (flag group_order_device)
     DBuf localBits, pullGather;                         // world > 1 pull: this shard's frontier bitmap, all shards' 
     struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
     std::vector<ngx_stat> statList;                     // ngx_stats view
@@ -2202,6 +2205,7 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "group_by_lds") *value = static_cast<int64_t>(c->groupByLds);
     else if (n == "group_lds_max") *value = c->groupLdsMax;
     else if (n == "order_by_device") *value = static_cast<int64_t>(c->orderByDevice);
+    else if (n == "group_order_device") *value = static_cast<int64_t>(c->groupOrderDevice);
     else if (n == "order_k_max") *value = c->orderKMax;
     else if (n == "group_grid_max") *value = c->groupGridMax;
     else if (n == "order_grid_max") *value = c->orderGridMax;
@@ -5711,18 +5715,40 @@ static_assert(sizeof(GroupCell) == sizeof(ngx_cell) && offsetof(GroupCell, v) ==
 
 bool intLike(int32_t t) { return t == NGX_T_INT || t == NGX_T_VID || t == NGX_T_TIMESTAMP; }
 
-int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupResultHolder& R) {
+// The grouping up to its state words, shared by ngx_go_group_by (which emits cells from it) and
+// ngx_go_group_order_by (which turns it into columns): groupPrepare checks the plan and lays out columns, state
+// slots and yield descriptors on the host; groupAccumulate runs assign + scan + accumulate and leaves the
+// device state in the context's gb* buffers.
+struct GroupStage {
+    uint64_t n = 0, ngroups = 0;
+    std::vector<GroupCol> cols;                                   // the result columns the kernels read
+    std::vector<int32_t> typeOf, keyIdx, distinctCol;             // distinctCol: value column of each COUNT_DISTINCT pass
+    std::vector<GroupSlot> slots;
+    std::vector<GroupEmit> emit;
+    std::vector<uint8_t> isCount;                                 // per yield: a COUNT / COUNT_DISTINCT state word, in [0, n]
+    GroupCol* colsDev = nullptr;
+    GroupSlot* slotsDev = nullptr;
+    GroupEmit* emitDev = nullptr;
+    uint32_t* leader = nullptr;
+    uint64_t* flag = nullptr;
+    uint64_t* pre = nullptr;
+    uint64_t* tiles = nullptr;
+    uint64_t* state = nullptr;
+    bool lds = false;
+};
+
+int32_t groupPrepare(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupStage& G) {
     if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "group by: not a device-resident result");
     if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "group by: world > 1 needs mergeable partial states");
     if (gp->nkeys < 1 || gp->nyields < 1 || !gp->key_cols || !gp->yields) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no key or yield columns");
     if (gp->nkeys > kGroupMaxKeys) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 4 keys");
     if (gp->nyields > kMaxDistinctCols) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 64 yields");
-    const uint64_t n = r->nrows;
+    const uint64_t n = G.n = r->nrows;
     if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "group by: 2^32 rows or more");
 
-    // the result columns the kernels read
-    std::vector<GroupCol> cols;
-    std::vector<int32_t> colOf(std::max<int32_t>(r->ncols, 1), -1), typeOf;
+    std::vector<GroupCol>& cols = G.cols;
+    std::vector<int32_t> colOf(std::max<int32_t>(r->ncols, 1), -1);
+    std::vector<int32_t>& typeOf = G.typeOf;
     auto useCol = [&](int32_t y, bool key, int32_t* idx) -> int32_t {
         if (y < 0 || y >= r->ncols) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no such result column");
         const int32_t t = r->col_types[y];
@@ -5747,14 +5773,17 @@ int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, Gr
         *idx = colOf[y];
         return NGX_OK;
     };
-    std::vector<int32_t> keyIdx(gp->nkeys);
+    std::vector<int32_t>& keyIdx = G.keyIdx;
+    keyIdx.assign(gp->nkeys, -1);
     for (int32_t k = 0; k < gp->nkeys; k++)
         if (int32_t rc = useCol(gp->key_cols[k], true, &keyIdx[k])) return rc;
 
     // per yield column: its state words and how its cell is finalised
-    std::vector<GroupSlot> slots;
-    std::vector<GroupEmit> emit(gp->nyields);
-    std::vector<int32_t> distinctCol;                            // value column of each COUNT_DISTINCT pass
+    std::vector<GroupSlot>& slots = G.slots;
+    std::vector<GroupEmit>& emit = G.emit;
+    std::vector<int32_t>& distinctCol = G.distinctCol;
+    emit.assign(gp->nyields, GroupEmit{});
+    G.isCount.assign(gp->nyields, 0);
     auto slot = [&](int32_t op, int32_t src, int32_t col) {
         GroupSlot s{};
         s.op = op, s.src = src, s.col = col;
@@ -5795,11 +5824,13 @@ int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, Gr
                 break;
             case NGX_AGG_COUNT:
                 e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcOne, -1);
+                G.isCount[y] = 1;
                 break;
             case NGX_AGG_COUNT_DISTINCT:
                 if (a.col < 0) { constant(e, NGX_CELL_INT, 1); break; }
                 e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcFlag, static_cast<int32_t>(distinctCol.size()));
                 distinctCol.push_back(ci);
+                G.isCount[y] = 1;
                 break;
             case NGX_AGG_SUM:
                 if (intLike(t)) e.kind = t, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcCol, ci);
@@ -5830,20 +5861,17 @@ int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, Gr
                 break;
         }
     }
-    R.r.ncols = gp->nyields;
-    R.colTypes.assign(gp->nyields, 0);
-    R.r.col_types = R.colTypes.data();
-    if (n == 0) {
-        c->groupByDevice++;
-        return NGX_OK;
-    }
-    for (int32_t y = 0; y < gp->nyields; y++) R.colTypes[y] = emit[y].kind;
+    return NGX_OK;
+}
 
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
+// assign + accumulate of a prepared stage with rows (G.n > 0)
+void groupAccumulate(ngx_ctx* c, const ngx_group_plan* gp, GroupStage& G) {
+    const uint64_t n = G.n;
+    std::vector<GroupCol>& cols = G.cols;
+    std::vector<GroupSlot>& slots = G.slots;
+    std::vector<GroupEmit>& emit = G.emit;
+    const std::vector<int32_t>& keyIdx = G.keyIdx;
+    const std::vector<int32_t>& distinctCol = G.distinctCol;
 
     // ---- assign: leaders, group numbers
     uint64_t cap = 1024;
@@ -5904,17 +5932,51 @@ int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, Gr
     c->timed(lds ? "group_accum_lds" : "group_accum", n * 8 * (slots.size() + 1), [&] {
         if (launchGroupAccum(ga, lds, c->groupGridMax, c->stream)) throw Error{NGX_E_DEVICE, "group accumulate"};
     });
+    G.ngroups = ngroups;
+    G.colsDev = colsDev, G.slotsDev = slotsDev, G.emitDev = emitDev;
+    G.leader = aa.leader, G.flag = aa.flag, G.pre = pre, G.tiles = tiles, G.state = ga.state;
+    G.lds = lds;
+}
+
+void groupEvents(ngx_ctx* c) {
+    HIP_OK(hipSetDevice(c->device));
+    for (hipEvent_t& e : c->gbEv)
+        if (!e) HIP_OK(hipEventCreate(&e));
+}
+
+int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupResultHolder& R) {
+    GroupStage G;
+    if (int32_t rc = groupPrepare(c, r, gp, G)) return rc;
+    const uint64_t n = G.n;
+    const std::vector<GroupCol>& cols = G.cols;
+    const std::vector<GroupEmit>& emit = G.emit;
+    R.r.ncols = gp->nyields;
+    R.colTypes.assign(gp->nyields, 0);
+    R.r.col_types = R.colTypes.data();
+    if (n == 0) {
+        c->groupByDevice++;
+        return NGX_OK;
+    }
+    for (int32_t y = 0; y < gp->nyields; y++) R.colTypes[y] = emit[y].kind;
+
+    groupEvents(c);
+    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
+    HIP_OK(hipEventRecord(ev0, c->stream));
+    groupAccumulate(c, gp, G);
+    const uint64_t ngroups = G.ngroups;
+    uint64_t* tiles = G.tiles;
+    const bool lds = G.lds;
 
     // ---- emit
     GroupEmitArgs ea{};
     ea.n = n;
     ea.ngroups = ngroups;
     ea.ny = gp->nyields;
-    ea.emit = emitDev;
-    ea.cols = colsDev;
-    ea.flag = aa.flag;
-    ea.pre = pre;
-    ea.state = ga.state;
+    ea.emit = G.emitDev;
+    ea.cols = G.colsDev;
+    ea.flag = G.flag;
+    ea.pre = G.pre;
+    ea.state = G.state;
     ea.cells = c->gbCells.get<GroupCell>(ngroups * gp->nyields);
     bool anyString = false;
     for (const GroupEmit& e : emit) anyString |= e.src == kEmitKey && cols[e.a].kind == kGroupString;
@@ -5990,14 +6052,23 @@ uint64_t orderDoubleKey(int64_t bits) {
     return b ^ (static_cast<uint64_t>(static_cast<int64_t>(b) >> 63) | 0x8000000000000000ULL);
 }
 
-int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, OrderResultHolder& R) {
-    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "order by: not a device-resident result");
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "order by: world > 1 needs the shards' winners merged");
+// the plan's own limits, before any column is looked at
+int32_t orderPlanCheck(ngx_ctx* c, const ngx_order_plan* op) {
     if (op->nfactors < 0 || (op->nfactors && !op->factors) || op->offset < 0) return fail(c, NGX_E_BAD_ARGUMENT, "order by: factors or offset");
     if (op->count < 0) return fail(c, NGX_E_UNSUPPORTED, "order by: no LIMIT (every row crosses anyway)");
     if (op->nfactors > kOrderMaxFactors) return fail(c, NGX_E_UNSUPPORTED, "order by: more than 8 factors");
     if (op->offset > c->orderKMax || op->count > c->orderKMax - op->offset)
         return fail(c, NGX_E_UNSUPPORTED, "order by: offset + count above order_k_max");
+    return NGX_OK;
+}
+
+int32_t orderRows(ngx_ctx* c, uint64_t n, int32_t ncols, const int32_t* types, const std::vector<OrderEmitCol>& ecols, bool anyString,
+                  const ngx_order_plan* op, bool started, OrderResultHolder& R);
+
+int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, OrderResultHolder& R) {
+    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "order by: not a device-resident result");
+    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "order by: world > 1 needs the shards' winners merged");
+    if (int32_t rc = orderPlanCheck(c, op)) return rc;
     const uint64_t n = r->nrows;
     if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "order by: 2^32 rows or more");
     const int32_t ncols = r->ncols;
@@ -6011,15 +6082,13 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
     R.r.ncols = ncols;
     R.colTypes.assign(r->col_types, r->col_types + ncols);
     R.r.col_types = R.colTypes.data();
-    const uint64_t offset = static_cast<uint64_t>(op->offset), K = offset + static_cast<uint64_t>(op->count);
-    if (op->count == 0 || offset >= n || ncols == 0) {           // the column names and no rows: nothing to launch
+    if (op->count == 0 || static_cast<uint64_t>(op->offset) >= n || ncols == 0) {   // the column names and no rows: nothing to launch
         c->orderByDevice++;
         return NGX_OK;
     }
 
     // every column as the emit kernel reads it; the factors' among them feed the levels
     std::vector<OrderEmitCol> ecols(ncols);
-    std::vector<GroupCol> cols(ncols);
     bool anyString = false;
     for (int32_t y = 0; y < ncols; y++) {
         const int32_t t = r->col_types[y];
@@ -6035,14 +6104,27 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
         if (e.c.w && !e.c.x) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column without values");
         if (e.c.w != 0 && e.c.w != 1 && e.c.w != 2 && e.c.w != 4 && e.c.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column width");
         anyString |= t == NGX_T_STRING || e.type != nullptr;
-        cols[y] = e.c;
     }
+    if (int32_t rc = orderRows(c, n, ncols, r->col_types, ecols, anyString, op, false, R)) return rc;
+    c->orderByDevice++;
+    return NGX_OK;
+}
+
+// Levels -> select -> emit -> host sort of the winners, over n rows of ncols columns as the kernels read them
+// (a GO result's columns for ngx_go_order_by, the group columns for ngx_go_group_order_by; types: NGX_T_* per
+// column). The window has rows (count > 0, offset < n, ncols > 0). started: the caller recorded gbEv[0] already
+// and device_ms counts from there.
+int32_t orderRows(ngx_ctx* c, uint64_t n, int32_t ncols, const int32_t* types, const std::vector<OrderEmitCol>& ecols, bool anyString,
+                  const ngx_order_plan* op, bool started, OrderResultHolder& R) {
+    const uint64_t offset = static_cast<uint64_t>(op->offset), K = offset + static_cast<uint64_t>(op->count);
+    std::vector<GroupCol> cols(ncols);
+    for (int32_t y = 0; y < ncols; y++) cols[y] = ecols[y].c;
 
     HIP_OK(hipSetDevice(c->device));
     for (hipEvent_t& e : c->gbEv)
         if (!e) HIP_OK(hipEventCreate(&e));
     const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
+    if (!started) HIP_OK(hipEventRecord(ev0, c->stream));
 
     // ---- the levels: per factor its words, then the row index
     std::vector<OrderLevel> levels;
@@ -6052,7 +6134,7 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
         return bits;
     };
     for (int32_t f = 0; f < op->nfactors; f++) {
-        const int32_t y = op->factors[f].col, t = r->col_types[y];
+        const int32_t y = op->factors[f].col, t = types[y];
         const int32_t desc = op->factors[f].desc ? 1 : 0;
         if (t == NGX_T_STRING) {
             uint32_t* mx = c->obMax.get<uint32_t>(1);
@@ -6061,7 +6143,7 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
             if (maxLen > kOrderMaxStr) return fail(c, NGX_E_UNSUPPORTED, "order by: a factor string longer than 256 bytes");
             for (uint32_t w = 0; w < (maxLen + 7) / 8; w++) levels.push_back(OrderLevel{y, kOrdStrWord, static_cast<int32_t>(w), desc, 64, 0});
             if (maxLen) levels.push_back(OrderLevel{y, kOrdStrLen, 0, desc, bitsFor(maxLen), 0});
-        } else if (t == NGX_T_DOUBLE || t == NGX_T_FLOAT) {
+        } else if ((t == NGX_T_DOUBLE || t == NGX_T_FLOAT) && cols[y].w) {
             levels.push_back(OrderLevel{y, kOrdDouble, 0, desc, 64, 0});
         } else if (cols[y].w) {                                   // width 0: a constant ties every row
             levels.push_back(OrderLevel{y, kOrdInt, 0, desc, cols[y].w * 8, 0});
@@ -6179,7 +6261,7 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
         const char* sbase = R.strings.data();
         auto less = [&](uint32_t a, uint32_t b) {
             for (int32_t f = 0; f < op->nfactors; f++) {
-                const int32_t y = op->factors[f].col, t = r->col_types[y];
+                const int32_t y = op->factors[f].col, t = types[y];
                 const ngx_cell* x = &cells[static_cast<uint64_t>(a) * ncols + y];
                 const ngx_cell* z = &cells[static_cast<uint64_t>(b) * ncols + y];
                 if (op->factors[f].desc) std::swap(x, z);
@@ -6208,7 +6290,93 @@ int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, Or
     R.r.cells = R.cells.data();
     R.r.strings = R.strings.data();
     R.r.strings_len = strBytes;
-    c->orderByDevice++;
+    return NGX_OK;
+}
+
+// GO | GROUP BY | [ORDER BY |] LIMIT: the grouping's state becomes columns (k_group_columns) and the select
+// reads those; only the window's group rows cross.
+int32_t groupOrderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, const ngx_order_plan* op, OrderResultHolder& R) {
+    GroupStage G;
+    if (int32_t rc = groupPrepare(c, r, gp, G)) return rc;
+    if (int32_t rc = orderPlanCheck(c, op)) return rc;
+    const int32_t ny = gp->nyields;
+    for (int32_t f = 0; f < op->nfactors; f++)
+        if (op->factors[f].col < 0 || op->factors[f].col >= ny) return fail(c, NGX_E_BAD_ARGUMENT, "order by: no such result column");
+    const uint64_t n = G.n;
+    R.r.ncols = ny;
+    R.colTypes.assign(ny, 0);
+    R.r.col_types = R.colTypes.data();
+    if (n == 0) {                                                 // no groups: nothing to launch
+        c->groupOrderDevice++;
+        return NGX_OK;
+    }
+    for (int32_t y = 0; y < ny; y++) R.colTypes[y] = G.emit[y].kind;
+
+    groupEvents(c);
+    HIP_OK(hipEventRecord(c->gbEv[0], c->stream));
+    groupAccumulate(c, gp, G);
+    const uint64_t ngroups = G.ngroups;
+    R.r.input_rows = ngroups;
+
+    // ---- the group rows as columns: a COUNT / COUNT_DISTINCT lies in [0, n] and takes the narrowest signed
+    // width that holds n (the select pays one step per byte of an integer factor); the rest 8 bytes
+    const int32_t countW = n <= 0x7F ? 1 : n <= 0x7FFF ? 2 : n <= 0x7FFFFFFF ? 4 : 8;
+    std::vector<GroupColumnOut> outs(ny);
+    std::vector<OrderEmitCol> ecols(ny);
+    uint64_t colBytes = 0, lenCols = 0;
+    bool anyString = false;
+    for (int32_t y = 0; y < ny; y++) {
+        const GroupEmit& e = G.emit[y];
+        OrderEmitCol& oc = ecols[y];
+        oc.cell = e.kind;                                         // NGX_CELL_* numbers its kinds as NGX_T_*
+        oc.c.kind = e.kind == NGX_T_STRING ? kGroupString : e.kind == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
+        oc.c.konst = e.konst;
+        oc.c.w = e.src == kEmitConst ? 0 : G.isCount[y] ? countW : 8;
+        outs[y].w = oc.c.w;
+        colBytes += (ngroups * static_cast<uint64_t>(oc.c.w) + 7) / 8 * 8;
+        if (oc.c.kind == kGroupString) lenCols++, anyString = true;
+    }
+    char* colMem = c->goCols.get<char>(std::max<uint64_t>(colBytes, 1));
+    uint32_t* lenMem = c->goLen.get<uint32_t>(std::max<uint64_t>(lenCols * ngroups, 1));
+    uint64_t at = 0, lenAt = 0;
+    for (int32_t y = 0; y < ny; y++) {
+        OrderEmitCol& oc = ecols[y];
+        if (!oc.c.w) continue;
+        outs[y].x = colMem + at;
+        oc.c.x = outs[y].x;
+        at += (ngroups * static_cast<uint64_t>(oc.c.w) + 7) / 8 * 8;
+        if (oc.c.kind == kGroupString) {
+            outs[y].len = lenMem + lenAt;
+            oc.c.len = outs[y].len;
+            lenAt += ngroups;
+        }
+    }
+    GroupColumnOut* outsDev = c->goDesc.get<GroupColumnOut>(ny);
+    HIP_OK(hipMemcpyAsync(outsDev, outs.data(), outs.size() * sizeof(GroupColumnOut), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vector is pageable: copied before it goes
+    GroupColumnsArgs ca{};
+    ca.n = n;
+    ca.ngroups = ngroups;
+    ca.ny = ny;
+    ca.emit = G.emitDev;
+    ca.cols = G.colsDev;
+    ca.flag = G.flag;
+    ca.pre = G.pre;
+    ca.state = G.state;
+    ca.out = outsDev;
+    c->timed("group_columns", n * 8 + colBytes + lenCols * ngroups * 4, [&] {
+        if (launchGroupColumns(ca, c->stream)) throw Error{NGX_E_DEVICE, "group columns"};
+    });
+
+    int32_t rc = NGX_OK;
+    if (op->count != 0 && static_cast<uint64_t>(op->offset) < ngroups)
+        rc = orderRows(c, ngroups, ny, R.colTypes.data(), ecols, anyString, op, true, R);
+    else
+        HIP_OK(hipStreamSynchronize(c->stream));
+    c->collectTimings();
+    if (rc) return rc;
+    c->groupOrderDevice++;
+    if (G.lds) c->groupByLds++;
     return NGX_OK;
 }
 
@@ -6232,4 +6400,21 @@ extern "C" int32_t ngx_go_order_by(ngx_ctx* c, const ngx_go_result* r, const ngx
 
 extern "C" void ngx_order_result_free(ngx_order_result* r) {
     if (r) delete reinterpret_cast<OrderResultHolder*>(r);
+}
+
+extern "C" int32_t ngx_go_group_order_by(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* group, const ngx_order_plan* order,
+                                         ngx_order_result** out) {
+    if (!c || !r || !group || !order || !out) return NGX_E_BAD_ARGUMENT;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto R = std::make_unique<OrderResultHolder>();
+    int32_t rc;
+    try {
+        rc = groupOrderBy(c, r, group, order, *R);
+    } catch (const Error& e) {
+        rc = fail(c, e.code, e.msg);
+    }
+    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
+    R->r.code = rc;
+    *out = &R.release()->r;
+    return rc;
 }

@@ -183,6 +183,20 @@ __global__ __launch_bounds__(256) void k_group_strlen(GroupEmitArgs a, uint64_t*
     slen[r] = total;
 }
 
+// the finalised value bits of a yield column kept in state words (every kEmit* but kEmitKey / kEmitConst)
+__device__ __forceinline__ int64_t gFinal(const GroupEmit& e, const uint64_t* state, uint64_t ngroups, uint64_t g) {
+    switch (e.src) {
+        case kEmitOrdered: return gOrderKey(static_cast<int64_t>(state[e.a * ngroups + g]));
+        case kEmitAvgInt:
+            return __double_as_longlong(static_cast<double>(static_cast<int64_t>(state[e.a * ngroups + g])) /
+                                        static_cast<double>(state[(e.a + 1) * ngroups + g]));
+        case kEmitAvgF64:
+            return __double_as_longlong(__longlong_as_double(static_cast<int64_t>(state[e.a * ngroups + g])) /
+                                        static_cast<double>(state[(e.a + 1) * ngroups + g]));
+        default: return static_cast<int64_t>(state[e.a * ngroups + g]);      // kEmitState
+    }
+}
+
 __global__ __launch_bounds__(256) void k_group_emit(GroupEmitArgs a) {
     const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n || !a.flag[r]) return;
@@ -210,19 +224,38 @@ __global__ __launch_bounds__(256) void k_group_emit(GroupEmitArgs a) {
                 }
                 break;
             }
-            case kEmitState: out.v = static_cast<int64_t>(a.state[e.a * a.ngroups + g]); break;
-            case kEmitOrdered: out.v = gOrderKey(static_cast<int64_t>(a.state[e.a * a.ngroups + g])); break;
-            case kEmitAvgInt:
-                out.v = __double_as_longlong(static_cast<double>(static_cast<int64_t>(a.state[e.a * a.ngroups + g])) /
-                                             static_cast<double>(a.state[(e.a + 1) * a.ngroups + g]));
-                break;
-            case kEmitAvgF64:
-                out.v = __double_as_longlong(__longlong_as_double(static_cast<int64_t>(a.state[e.a * a.ngroups + g])) /
-                                             static_cast<double>(a.state[(e.a + 1) * a.ngroups + g]));
-                break;
-            default: out.v = e.konst; break;                      // kEmitConst
+            case kEmitConst: out.v = e.konst; break;
+            default: out.v = gFinal(e, a.state, a.ngroups, g); break;
         }
         a.cells[g * a.ny + y] = out;
+    }
+}
+
+// the group rows as columns: one thread per leader row writes one value per yield column at its group id
+// (what k_group_emit writes as cells; the same expressions, so the bits are equal)
+__global__ __launch_bounds__(256) void k_group_columns(GroupColumnsArgs a) {
+    const uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (r >= a.n || !a.flag[r]) return;
+    const uint64_t g = a.pre[r];
+    if (g >= a.ngroups) return;
+    for (int y = 0; y < a.ny; y++) {
+        const GroupColumnOut o = a.out[y];
+        if (!o.x) continue;                                       // kEmitConst: the column has no array
+        const GroupEmit e = a.emit[y];
+        int64_t v;
+        if (e.src == kEmitKey) {
+            const GroupCol& c = a.cols[e.a];
+            v = gRead(c, r);
+            if (o.len) o.len[g] = c.len ? c.len[r] : 0;
+        } else {
+            v = gFinal(e, a.state, a.ngroups, g);
+        }
+        switch (o.w) {
+            case 1: static_cast<int8_t*>(o.x)[g] = static_cast<int8_t>(v); break;
+            case 2: static_cast<int16_t*>(o.x)[g] = static_cast<int16_t>(v); break;
+            case 4: static_cast<int32_t*>(o.x)[g] = static_cast<int32_t>(v); break;
+            default: static_cast<int64_t*>(o.x)[g] = v; break;
+        }
     }
 }
 
@@ -262,6 +295,13 @@ int launchGroupStrLen(const GroupEmitArgs& a, uint64_t* slen, hipStream_t s) {
 int launchGroupEmit(const GroupEmitArgs& a, hipStream_t s) {
     if (a.n == 0) return 0;
     hipLaunchKernelGGL(k_group_emit, dim3(static_cast<unsigned>((a.n + 255) / 256)), dim3(256), 0, s, a);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launchGroupColumns(const GroupColumnsArgs& a, hipStream_t s) {
+    if (a.n == 0 || a.ngroups == 0) return 0;
+    if (a.ny < 1 || !a.out) return 1;
+    hipLaunchKernelGGL(k_group_columns, dim3(static_cast<unsigned>((a.n + 255) / 256)), dim3(256), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 

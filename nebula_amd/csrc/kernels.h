@@ -434,6 +434,28 @@ struct GroupEmitArgs {
 };
 int launchGroupStrLen(const GroupEmitArgs& a, uint64_t* slen, hipStream_t s);
 int launchGroupEmit(const GroupEmitArgs& a, hipStream_t s);
+// the group rows as columns instead of cells (ngx_go_group_order_by: the radix select of orderby.hip reads them
+// in place as GroupCols). One array of ngroups values per yield column, indexed by the group id: `w` bytes a
+// value (8, or the narrowest signed width that holds the input's row count for a COUNT / COUNT_DISTINCT); a
+// string key keeps its bytes where they are and writes its device pointer (8 bytes) and its length.
+// x null: a constant yield, no array (the column has width 0).
+struct GroupColumnOut {
+    void* x;
+    uint32_t* len;                      // string key columns only
+    int32_t w;                          // 1 / 2 / 4 / 8
+    int32_t pad;
+};
+struct GroupColumnsArgs {
+    uint64_t n, ngroups;
+    int32_t ny;
+    const GroupEmit* emit;              // device arrays
+    const GroupCol* cols;
+    const uint64_t* flag;
+    const uint64_t* pre;
+    const uint64_t* state;
+    const GroupColumnOut* out;          // ny entries
+};
+int launchGroupColumns(const GroupColumnsArgs& a, hipStream_t s);
 // ORDER BY ... LIMIT over a device-resident result (orderby.hip; ngx_go_order_by): the K first rows of the
 // order are selected by an MSD radix select over levels. A level is one order-preserving unsigned word per
 // row of `bits` significant bits (a multiple of 8), consumed 8 bits a step from the top:

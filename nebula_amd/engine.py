@@ -239,6 +239,7 @@ SIGNATURES = {
     "ngx_group_result_free": (None, [P(GroupResultC)]),
     "ngx_go_order_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(OrderPlanC), P(P(OrderResultC))]),
     "ngx_order_result_free": (None, [P(OrderResultC)]),
+    "ngx_go_group_order_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GroupPlanC), P(OrderPlanC), P(P(OrderResultC))]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
     "ngx_kernel_stats": (c_i32, [ctypes.c_void_p, P(P(KernelStat)), P(c_i32)]),
     "ngx_set_flag": (c_i32, [ctypes.c_void_p, ctypes.c_char_p, c_i64]),
@@ -368,6 +369,7 @@ class GoResult:
     # order_by: the selection's device time and the library's host sort of the winners (go_* as for group_by)
     order_device_ms: float = 0.0
     order_host_sort_ms: float = 0.0
+    ngroups: int = 0                     # group_by + order_by: the groups the window was cut from
 
 
 @dataclass
@@ -408,6 +410,7 @@ class PreparedGo:
 class Engine:
     device_group_by = True                     # go(..., group_by=...) groups a device-resident result (pipeline.py)
     device_order_by = True                     # go(..., order_by=...) selects a device-resident result's top rows
+    device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -580,7 +583,10 @@ class Engine:
         result with that code and the reason (the caller groups on the host), not as an exception.
         order_by: likewise, rows [offset, offset + count) of the result ordered by the spec's factors are
         selected in HBM (ngx_go_order_by); GoResult.rows / nrows are those rows in order, col_types the GO's,
-        device_ms / order_device_ms the selection's, order_host_sort_ms the library's sort of the winners."""
+        device_ms / order_device_ms the selection's, order_host_sort_ms the library's sort of the winners.
+        group_by and order_by together: the group rows are ordered and cut in HBM too (ngx_go_group_order_by;
+        the spec's factors name yield columns of group_by); rows / nrows / col_types describe the window of
+        group rows, device_ms / group_device_ms / order_device_ms are the one call's time."""
         if group_by is not None or order_by is not None:
             on_device, columnar = True, False
         if isinstance(s, PreparedGo):                       # its own pushdown / result-placement flags
@@ -617,7 +623,9 @@ class Engine:
                     # width 0: a constant column (value in dev_key_const / dev_col_const, no array)
                     res.dev_widths = (r.dev_key_w[:3], r.dev_col_w[:nc] if nc else [])
                     res.dev_consts = (r.dev_key_const[:3], r.dev_col_const[:nc] if nc and r.dev_col_const else [0] * nc)
-                if group_by is not None and rc == 0:
+                if group_by is not None and order_by is not None and rc == 0:
+                    self._group_order_by(out, group_by, order_by, res)
+                elif group_by is not None and rc == 0:
                     self._group_by(out, group_by, res)
                 elif order_by is not None and rc == 0:
                     self._order_by(out, order_by, res)
@@ -668,7 +676,9 @@ class Engine:
         finally:
             self.L.ngx_go_result_free(out)
 
-    def _group_by(self, go_out, spec: GroupBySpec, res: GoResult):
+    @staticmethod
+    def _group_plan(spec: GroupBySpec):
+        """(GroupPlanC, the arrays it points into)"""
         keys = (c_i32 * max(1, len(spec.key_cols)))(*spec.key_cols)
         ys = (AggColC * max(1, len(spec.yields)))()
         for i, (fn, col, konst) in enumerate(spec.yields):
@@ -680,7 +690,17 @@ class Engine:
                     ys[i].konst.kind, ys[i].konst.v.i = _CELL_KIND["int"], konst
                 else:
                     ys[i].konst.kind = _CELL_KIND["str"]
-        plan = GroupPlanC(len(spec.key_cols), keys, len(spec.yields), ys)
+        return GroupPlanC(len(spec.key_cols), keys, len(spec.yields), ys), (keys, ys)
+
+    @staticmethod
+    def _order_plan(spec: OrderBySpec):
+        fs = (OrderFactorC * max(1, len(spec.factors)))()
+        for i, (col, desc) in enumerate(spec.factors):
+            fs[i].col, fs[i].desc = col, 1 if desc else 0
+        return OrderPlanC(len(spec.factors), fs, spec.offset, spec.count), fs
+
+    def _group_by(self, go_out, spec: GroupBySpec, res: GoResult):
+        plan, _keep = self._group_plan(spec)
         gout = P(GroupResultC)()
         rc = self.L.ngx_go_group_by(self.h, go_out, ctypes.byref(plan), ctypes.byref(gout))
         try:
@@ -700,13 +720,14 @@ class Engine:
         finally:
             self.L.ngx_group_result_free(gout)
 
-    def _order_by(self, go_out, spec: OrderBySpec, res: GoResult):
-        fs = (OrderFactorC * max(1, len(spec.factors)))()
-        for i, (col, desc) in enumerate(spec.factors):
-            fs[i].col, fs[i].desc = col, 1 if desc else 0
-        plan = OrderPlanC(len(spec.factors), fs, spec.offset, spec.count)
+    def _order_by(self, go_out, spec: OrderBySpec, res: GoResult, group: Optional[GroupBySpec] = None):
+        plan, _keep = self._order_plan(spec)
         oout = P(OrderResultC)()
-        rc = self.L.ngx_go_order_by(self.h, go_out, ctypes.byref(plan), ctypes.byref(oout))
+        if group is not None:
+            gplan, _gkeep = self._group_plan(group)
+            rc = self.L.ngx_go_group_order_by(self.h, go_out, ctypes.byref(gplan), ctypes.byref(plan), ctypes.byref(oout))
+        else:
+            rc = self.L.ngx_go_order_by(self.h, go_out, ctypes.byref(plan), ctypes.byref(oout))
         try:
             res.go_device_ms, res.go_nrows = res.device_ms, res.nrows
             if rc:
@@ -722,8 +743,15 @@ class Engine:
             res.nrows = o.nrows
             res.device_ms = res.order_device_ms = o.device_ms
             res.order_host_sort_ms = o.host_sort_ms
+            if group is not None:
+                res.group_device_ms, res.ngroups = o.device_ms, o.input_rows
+                if not o.input_rows:
+                    res.col_types = []
         finally:
             self.L.ngx_order_result_free(oout)
+
+    def _group_order_by(self, go_out, group: GroupBySpec, order: OrderBySpec, res: GoResult):
+        self._order_by(go_out, order, res, group=group)
 
     def go_batch(self, prepared: Sequence["PreparedGo"], digests: bool = False):
         """Run prepared GO plans back to back in one native call (ngx_go_batch): per query (code, result

@@ -16,6 +16,8 @@ library, include/nebula_gn.h ngx_go with input_* set):
   - OrderByExecutor / LimitExecutor (src/graph/OrderByExecutor.cpp, LimitExecutor.cpp): `... | ORDER BY
     <factors>` and `... | LIMIT [off,] n` over the left side's interim result (nebula_amd/orderby.py), when
     the caller opts in with order_limit=True.
+  - A head `GO | GROUP BY | [ORDER BY |] LIMIT` runs in one device call where the backend has it
+    (ngx_go_group_order_by; Pipeline._go_group_order_by), also under order_limit=True.
 GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
 default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
@@ -132,11 +134,14 @@ class Pipeline:
     """Runs nGQL text made of GO sentences, pipes, parentheses, `$v = ...' and `;'."""
 
     def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
-                 order_limit: bool = False, device_order_by: bool = True, **go_kw):
+                 order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True, **go_kw):
         """device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device.
         order_limit=True: ORDER BY and LIMIT sentences run (off by default: they are refused like every
         sentence outside this path); device_order_by=False: `GO | ORDER BY | LIMIT` and `GO | LIMIT` order
-        and cut on the host even where the backend could select the rows on the device."""
+        and cut on the host even where the backend could select the rows on the device.
+        device_group_order=False: `GO | GROUP BY | [ORDER BY |] LIMIT` groups on the device and orders the group
+        rows on the host, even where the backend could do both in one call (it takes all three switches on)."""
+        self.device_group_order = device_group_order
         self.device_group_by = device_group_by
         self.order_limit = order_limit
         self.device_order_by = device_order_by
@@ -323,6 +328,57 @@ class Pipeline:
         # the interim schema the host path would hand on: UNKNOWN columns take the first row's type
         return Outcome(True, "", names, Interim.from_result(names, r.col_types, r.rows).types, list(r.rows))
 
+    def _group_order_spec(self, go_text: str, gb_text: str, ob_text: Optional[str], lim_text: Optional[str]):
+        """(GoSentence, GroupBySentence, group spec, order spec) when `GO | GROUP BY | ORDER BY | LIMIT` (ob_text
+        None: `GO | GROUP BY | LIMIT`) can run on the device in one call (ngx_go_group_order_by): _device_spec's
+        conditions, factors that name columns of the GROUP BY, and those names unique. ORDER BY without LIMIT
+        (lim_text None) is not sent: every group row would cross anyway. None: the paths there were decide."""
+        from .engine import OrderBySpec
+        if lim_text is None:
+            return None
+        plan = self._device_spec(go_text, gb_text)
+        if plan is None:
+            return None
+        s, g, gspec = plan
+        try:
+            lim = ngql.parse_limit(lim_text)
+            names = g.column_names()
+            factors = []
+            if ob_text is not None:
+                for col, desc in ngql.parse_order_by(ob_text).factors:
+                    if col not in names or names.count(col) != 1:
+                        return None
+                    factors.append((names.index(col), desc))
+            return s, g, gspec, OrderBySpec(factors, lim.offset, lim.count)
+        except (SyntaxError, ValueError):
+            return None
+
+    _HOST = object()                                              # _go_group_order_by: the plain host path has to run
+
+    def _go_group_order_by(self, go_text: str, gb_text: str, ob_text: Optional[str], lim_text: Optional[str]):
+        """`GO | GROUP BY | [ORDER BY |] LIMIT` on the device in one call. None: not sent, or refused by the order
+        stage ("order by: ..."): the device GROUP BY and the host sentences run as without this path. _HOST:
+        refused by the group stage ("group by: ..."), which the device GROUP BY would refuse again: every
+        sentence runs on the host. Either way a refusal costs one extra traversal."""
+        plan = self._group_order_spec(go_text, gb_text, ob_text, lim_text)
+        if plan is None:
+            return None
+        s, g, gspec, ospec = plan
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            r = self.backend.go(self.space, s, group_by=gspec, order_by=ospec, yield_only=True, compact=True, **kw)
+        except RuntimeError as e:
+            if getattr(e, "code", 0) == -1002:                    # the device-resident GO itself: the plain path decides
+                return self._HOST
+            raise
+        if not r.ok:
+            if r.code == -1002:                                   # NGX_E_UNSUPPORTED
+                return None if r.error.startswith("order by:") else self._HOST
+            return Outcome(False, r.error, s.column_names(self.edge_names))
+        # the interim schema the host path would hand on
+        names = g.column_names()
+        return Outcome(True, "", names, Interim.from_result(names, r.col_types, r.rows).types, list(r.rows))
+
     def _order_by(self, text: str, inp: Optional[Interim]) -> Outcome:
         """An ORDER BY sentence on the pipe's input: OrderByExecutor restated on the host (orderby.order_by)."""
         try:
@@ -371,6 +427,23 @@ class Pipeline:
                 if not skip and i + 1 < len(parts):
                     cur = Interim.from_result(out.names, out.col_types, out.rows)
                 continue
+            host_group = False
+            if self.order_limit and self.device_order_by and self.device_group_by and self.device_group_order \
+                    and getattr(self.backend, "device_group_order", False) and i + 2 < len(parts) \
+                    and body.upper().startswith("GO") and ngql.is_group_by(_unwrap(parts[i + 1])):
+                nxt = [_unwrap(p) for p in parts[i + 1:i + 4]]
+                dev, took = None, 0
+                if ngql.is_limit(nxt[1]):
+                    dev, took = self._go_group_order_by(body, nxt[0], None, nxt[1]), 2
+                elif len(nxt) == 3 and ngql.is_order_by(nxt[1]) and ngql.is_limit(nxt[2]):
+                    dev, took = self._go_group_order_by(body, nxt[0], nxt[1], nxt[2]), 3
+                if dev is self._HOST:
+                    host_group = True
+                elif dev is not None:
+                    out, skip = dev, took
+                    if not out.ok:
+                        return out
+                    continue
             if self.order_limit and self.device_order_by and getattr(self.backend, "device_order_by", False) \
                     and i + 1 < len(parts) and body.upper().startswith("GO"):
                 nxt = [_unwrap(p) for p in parts[i + 1:i + 3]]
@@ -384,7 +457,7 @@ class Pipeline:
                     if not out.ok:
                         return out
                     continue
-            if self.device_group_by and getattr(self.backend, "device_group_by", False) and i + 1 < len(parts) \
+            if not host_group and self.device_group_by and getattr(self.backend, "device_group_by", False) and i + 1 < len(parts) \
                     and body.upper().startswith("GO") and ngql.is_group_by(_unwrap(parts[i + 1])):
                 dev = self._go_group_by(body, _unwrap(parts[i + 1]))
                 if dev is not None:
@@ -432,6 +505,6 @@ class Pipeline:
 
 
 def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
-        order_limit: bool = False, device_order_by: bool = True, **go_kw) -> Outcome:
+        order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True, **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
-                    device_order_by=device_order_by, **go_kw).run(text)
+                    device_order_by=device_order_by, device_group_order=device_group_order, **go_kw).run(text)
