@@ -636,6 +636,10 @@ int32_t ngx_kernel_stats(ngx_ctx* ctx, const ngx_kernel_stat** out, int32_t* n);
  *          instead of a launch of its own. Same results.
  *          "dense_world_dev" 1 (default): at world > 1 too, that total stays on the device (published with
  *          the row count) instead of a host wait after the count launch. Same results.
+ *          "dense_early_loads" 1 (default): a generated kernel whose query reads no src row (one OVER type,
+ *          single-load YIELD columns) issues the edge-column loads of a dense final hop before it builds the
+ *          frontier bits from the marks; 0: the generic body. Read-only "dense_early_finals" (launches that
+ *          took it), "jit_dense_vgprs" / "jit_dense_scratch" (that kernel's registers and scratch). Same results.
  *   "final_nt_loads" / "final_nt_stores"  0 (default) / 1: the generated GO final hop loads its columns /
  *          stores its rows non-temporally (not kept in L2). Same results.
  * Read-only counters for ngx_get_flag: "jit_compiled", "jit_hits", "jit_failed", "jit_compile_us",

@@ -508,6 +508,10 @@ struct ngx_ctx {
     bool denseCloseTotal = true;                        // its frontier total summed by the close (flag dense_close_total)
     bool denseWorldDev = true;                          // world > 1: its totals kept on the device (flag dense_world_dev)
     uint64_t denseFinals = 0;
+    // a dense final hop of an eligible generated kernel (jit.h jitDenseEligible) issues its edge-column loads
+    // ahead of the frontier bits (final_kernels.h finalBodyDense; flag dense_early_loads); 0: the generic body
+    bool denseEarlyLoads = true;
+    uint64_t denseEarlyFinals = 0;                      // launches that took it (flag dense_early_finals, read-only)
     uint64_t dstReplicaMax = uint64_t(1) << 30;
     uint64_t dstFetches = 0, dstFetchRows = 0;
     ~ngx_ctx() {                                       // also the cleanup of ngx_open's error paths
@@ -2103,6 +2107,7 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
         return NGX_OK;
     }
     if (n == "dense_final") { c->denseFinal = value != 0; return NGX_OK; }
+    if (n == "dense_early_loads") { c->denseEarlyLoads = value != 0; return NGX_OK; }
     if (n == "dense_close_total") { c->denseCloseTotal = value != 0; return NGX_OK; }
     if (n == "dense_world_dev") { c->denseWorldDev = value != 0; return NGX_OK; }
     if (n == "dst_replica_max") { c->dstReplicaMax = static_cast<uint64_t>(std::max<int64_t>(value, 0)); return NGX_OK; }
@@ -2180,6 +2185,8 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "dense_close_total") *value = c->denseCloseTotal ? 1 : 0;
     else if (n == "dense_world_dev") *value = c->denseWorldDev ? 1 : 0;
     else if (n == "dense_finals") *value = static_cast<int64_t>(c->denseFinals);
+    else if (n == "dense_early_loads") *value = c->denseEarlyLoads ? 1 : 0;
+    else if (n == "dense_early_finals") *value = static_cast<int64_t>(c->denseEarlyFinals);
     else if (n == "dst_replica_max") *value = static_cast<int64_t>(c->dstReplicaMax);
     else if (n == "dst_fetches") *value = static_cast<int64_t>(c->dstFetches);
     else if (n == "dst_fetch_rows") *value = static_cast<int64_t>(c->dstFetchRows);
@@ -2220,6 +2227,8 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "jit_compile_us") *value = static_cast<int64_t>(c->jit.compileSeconds * 1e6);
     else if (n == "jit_vgprs") *value = c->jit.lastRegs;          // registers / scratch of the last compiled
     else if (n == "jit_scratch") *value = c->jit.lastScratch;     // final-hop kernel (occupancy check)
+    else if (n == "jit_dense_vgprs") *value = c->jit.lastDenseRegs;      // ... and of its module's loads-first
+    else if (n == "jit_dense_scratch") *value = c->jit.lastDenseScratch; // dense kernel (-1: the shape has none)
     else return fail(c, NGX_E_BAD_ARGUMENT, "unknown flag " + n);
     return NGX_OK;
 }
@@ -3952,7 +3961,11 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                 if (grid == 0) return;
                 if (kj) {
                     void* args[] = {&a};
-                    HIP_OK(hipModuleLaunchKernel(kj->final, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
+                    // dense (one slot, the grid = the slot's chunks): the loads-first body when the module has it
+                    const bool early = a.denseMark != nullptr && kj->finalDense != nullptr && c->denseEarlyLoads &&
+                                       a.fin == nullptr && a.hs.n == 1;
+                    if (early) c->denseEarlyFinals++;
+                    HIP_OK(hipModuleLaunchKernel(early ? kj->finalDense : kj->final, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
                 } else if (launchFinal(a, c->stream, grid)) {
                     throw Error{NGX_E_DEVICE, "final"};
                 }
@@ -5110,6 +5123,10 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
         streamAfter(ctxStream, roles[1], c->pipeEv[1]);
         streamAfter(ctxStream, roles[2], c->pipeEv[3]);
         streamAfter(ctxStream, roles[3], c->pipeEv[4]);
+        // every lane's last close is ordered before whatever comes next (the next batch's streams start after
+        // ctxStream): its final hops need not wait for these events again. Not earlier: a query has finished
+        // once it has read its row count, which its close publishes before it has moved the last rows
+        for (bool& pending : c->laneClosePending) pending = false;
     } catch (const Error& e) {
         if (first == NGX_OK) first = fail(c, e.code, e.msg);
     }

@@ -24,6 +24,8 @@ namespace ngx {
 struct JitKernels {
     hipModule_t mod = nullptr;
     hipFunction_t final = nullptr;      // the fused final-hop kernel (final_kernels.h finalBody)
+    hipFunction_t finalDense = nullptr; // eligible shapes (jitDenseEligible): the dense final hop with the edge
+                                        // loads ahead of the frontier bits (finalBodyDense); else nullptr
 };
 
 // one compiled program segment of a query: code[off ...] up to OP_END
@@ -82,6 +84,7 @@ public:
     uint64_t compiled = 0, hits = 0, failed = 0, evicted = 0;
     double compileSeconds = 0;
     int64_t lastRegs = -1, lastScratch = -1;    // hipFuncGetAttribute of the last compiled kernel
+    int64_t lastDenseRegs = -1, lastDenseScratch = -1;   // ... and of its module's ngx_jit_final_dense (-1: none)
     size_t capacity = 64;
     bool async = false;
     int device = 0;                             // HIP device the background thread loads modules on
@@ -90,7 +93,7 @@ public:
 private:
     struct Entry { std::shared_ptr<JitKernels> k; uint64_t used = 0; };
     std::vector<hipModule_t> retired_;
-    struct Done { std::string shape; JitKernels k; std::string err; double seconds; int64_t regs, scratch; };
+    struct Done { std::string shape; JitKernels k; std::string err; double seconds; int64_t regs[4]; };   // regs, scratch; dense
     void admit();                               // finished background compiles -> cache_ / failures_
     void insert(const std::string& shape, const JitKernels& k);
     uint64_t tick_ = 0;
@@ -113,5 +116,8 @@ std::string jitSource(const Space& sp, const JitQuery& q);
 // everything jitSource depends on, compactly: snapshot generation, programs (slotted literals as slot
 // numbers), column types, key aliases, hop flags
 std::string jitShapeKey(const Space& sp, const JitQuery& q);
+// whether the query's module also carries ngx_jit_final_dense: one slot, GO (no frontier index, no input
+// table), no src row read, every stored YIELD column one load (the evaluator is flat and eager)
+bool jitDenseEligible(const JitQuery& q);
 
 }  // namespace ngx
