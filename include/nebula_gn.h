@@ -547,6 +547,79 @@ void ngx_order_result_free(ngx_order_result* r);
 int32_t ngx_go_group_order_by(ngx_ctx* ctx, const ngx_go_result* r, const ngx_group_plan* group,
                               const ngx_order_plan* order, ngx_order_result** out);
 
+/* ---------------------------------------------------------------- UNION / INTERSECT / MINUS of two GO results */
+/* `GO ... UNION [DISTINCT] GO ...`, `GO ... INTERSECT GO ...` and `GO ... MINUS GO ...` with the set operator on
+ * the device: replaces SetExecutor::doUnion with doDistinct (src/graph/SetExecutor.cpp:200-252, 300-304),
+ * doIntersect (:306-354) and doMinus (:356-410), whose INTERSECT and MINUS are nested loops over both row
+ * vectors, for two results that stayed in HBM. Only the cells and string bytes of the output rows cross PCIe.
+ *
+ * ngx_set_op is the kernel stage: `left` and `right` are result_on_device results of this context that are both
+ * valid when it is called (ngx_go_set below arranges that; a test may hand it any columns in HBM). It reads
+ * code, nrows, ncols, col_types, dev_cols, dev_col_w and dev_col_const of either result.
+ * Row equality is the thrift ColumnValue ==, over every column: integers by value whatever width either side
+ * stores them at; doubles by value, so -0.0 equals 0.0 and a row holding a NaN equals no row, itself included;
+ * strings by length and bytes, wherever they lie.
+ *   NGX_SET_UNION_DISTINCT  one row of every distinct value of either side, and every NaN row. Order: the kept
+ *                           left rows in left order, then the kept right rows in right order. Which of several
+ *                           equal rows is kept is free (the row that claimed the table slot); equal rows are
+ *                           equal in every column, so only the multiset of rows is guaranteed, and that is the
+ *                           reference's, whose std::sort + std::unique fix the set and not its order.
+ *   NGX_SET_INTERSECT       a value occurring cL times left and cR times right comes out min(cL, cR) times
+ *                           (doIntersect moves each matched right row out, so it matches once), in left order.
+ *                           Which of the equal left rows are kept is free; they are indistinguishable, so the
+ *                           rows are exactly the reference's.
+ *   NGX_SET_MINUS           the left rows that equal no right row, duplicates included, in left order.
+ *   NGX_SET_UNION_ALL       refused (NGX_E_UNSUPPORTED): it needs no kernel, the caller concatenates.
+ * The result carries the left side's col_types (the caller names the columns as the left side's). With both
+ * sides empty: no rows. With one side empty the reference's shortcuts apply and no table is built: UNION hands
+ * the other side through as it is (not made distinct, under the other side's col_types), INTERSECT and MINUS
+ * with an empty left give no rows, MINUS with an empty right gives the left unchanged.
+ * Different column counts: NGX_E_BAD_ARGUMENT with the reference's text "Field count not match.".
+ * NGX_E_UNSUPPORTED, with a reason in ngx_last_error that starts "set op:", for: a column pair whose static
+ * types differ (InterimResult::castTo stays on the host), an UNKNOWN-typed (per-row type) column on either
+ * side, more than 16 columns, a string longer than 256 bytes, world > 1 (the shards' tables are not merged
+ * yet), 2^31 rows or more on a side, output rows above the flag "set_rows_max" (default 1 << 20, settable 1 ..
+ * 2^28: the point is rows that do not cross; found after the probe). The caller then runs the host path.
+ *
+ * ngx_go_set is the product call: both traversals with their results left in HBM (both plans result_on_device,
+ * without DISTINCT or input), then ngx_set_op, then both results freed. A device-resident result is valid until
+ * the next call on the context, so the right traversal runs on the second query lane (scratch, result rows and
+ * reservation state of its own, as ngx_go_batch's lanes) and builds its strings in arenas of its own: the left
+ * result is not copied. The traversals run one after the other. A traversal's error is the call's (code and
+ * ngx_last_error as ngx_go's). Memory: as a two-lane batch, the second lane's buffers stay with the context
+ * (flag "release_lanes").
+ * Flags: "set_op_device" (read-only) counts the set calls completed on the device; "set_rows_max"; "set_grid_max"
+ * (0, the default: built-in 2048, else 1 .. 2048) caps the workgroups of the build and probe kernels (256 rows a
+ * workgroup and sweep); read-only "set_loop_flushes" (a workgroup's LDS row-id buffer emptied inside its sweep
+ * loop: it kept more than 1792 rows). Same results under every setting. "set_check_left" 1 (debug, default 0):
+ * ngx_go_set takes ngx_go_result_digest of the left result before and after the right traversal and fails with
+ * NGX_E_DEVICE if they differ (integer / double / bool results); read-only "set_left_checks" counts the digests
+ * that agreed. ngx_kernel_stats: launch groups "set_build", "set_probe", "set_emit". */
+#define NGX_SET_UNION_DISTINCT 0
+#define NGX_SET_INTERSECT 1
+#define NGX_SET_MINUS 2
+#define NGX_SET_UNION_ALL 3
+typedef struct {
+    int32_t op;                        /* NGX_SET_* */
+} ngx_set_plan;
+typedef struct {
+    int32_t code;
+    int32_t ncols;
+    const int32_t* col_types;          /* NGX_T_* per column */
+    uint64_t nrows;
+    const ngx_cell* cells;             /* cells[row * ncols + col] */
+    const char* strings;
+    uint64_t strings_len;
+    uint64_t left_rows;                /* rows of the two inputs */
+    uint64_t right_rows;
+    double device_ms;                  /* HIP-event time of the set operator, table clear to the last cell */
+} ngx_set_result;
+int32_t ngx_set_op(ngx_ctx* ctx, const ngx_go_result* left, const ngx_go_result* right, const ngx_set_plan* plan,
+                   ngx_set_result** out);
+int32_t ngx_go_set(ngx_ctx* ctx, const ngx_go_plan* left, const ngx_go_plan* right, const ngx_set_plan* plan,
+                   ngx_set_result** out);
+void ngx_set_result_free(ngx_set_result* r);
+
 /* ---------------------------------------------------------------- measurement hooks */
 /* Per-kernel device times of the last ngx_go (HIP events on the engine stream), for bench.py. */
 typedef struct {

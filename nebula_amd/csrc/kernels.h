@@ -540,6 +540,38 @@ struct OrderEmitArgs {
 };
 int launchOrderStrLen(const OrderEmitArgs& a, uint64_t* slen, hipStream_t s);
 int launchOrderEmit(const OrderEmitArgs& a, hipStream_t s);
+// UNION DISTINCT / INTERSECT / MINUS over two device-resident results (setop.hip; ngx_set_op). Rows are named
+// by one id over both sides: left row r is r, right row r is nL + r (nL + nR < 2^32 - 1). The table holds
+// hash tag | id + 1 per slot, keyed on the whole row tuple (every column; as k_group_assign keys its key
+// columns): integers compare sign-extended from their stored widths, so one value stored at two widths on the
+// two sides is one key; doubles by value (-0.0 == 0.0); strings by length and bytes. A row with a NaN in any
+// double column equals no row, itself included: it is never inserted and never found.
+constexpr int kSetMaxCols = 16;
+constexpr uint32_t kSetGridMax = 2048;              // workgroups (of 256 rows a sweep) of the build / probe kernels
+enum { kSetUnionDistinct = 0, kSetIntersect = 1, kSetMinus = 2 };
+struct SetState {
+    uint64_t fill[2];                   // row ids appended to keep[side]: one atomicAdd per LDS buffer flush
+    uint32_t err;                       // a table without a free slot, a list past its capacity: cannot be
+    uint32_t loopFlushes;               // LDS buffer flushes inside a sweep loop of k_set_probe
+};
+struct SetArgs {
+    uint64_t n[2];                      // rows of the left / right result
+    const GroupCol* cols[2];            // device arrays, nc columns each
+    int32_t nc;
+    int32_t op;                         // kSet*
+    uint64_t* table;                    // mask + 1 slots >= 2 * the rows inserted, a power of two, zeroed
+    uint64_t mask;
+    uint32_t* count;                    // kSetIntersect: per slot the rows equal to its leader (zeroed), else null
+    uint32_t* taken;                    // kSetIntersect: per slot the tickets handed out (zeroed)
+    uint32_t* keep[2];                  // kept rows of each side (local row ids), n[side] entries each, in no order
+    SetState* S;
+    uint32_t gridMax;                   // most workgroups of a sweep (flag set_grid_max); 0: kSetGridMax
+};
+// every row of `side` goes into the table: the row that claims a slot leads, count[slot] counts the rows equal to it
+int launchSetBuild(const SetArgs& a, int side, hipStream_t s);
+// every row of `side` looks its tuple up. kSetMinus keeps the rows not found; kSetIntersect those whose ticket
+// (atomicAdd on taken[slot]) is below count[slot]; kSetUnionDistinct the rows that lead their slot (and NaN rows)
+int launchSetProbe(const SetArgs& a, int side, hipStream_t s);
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

@@ -205,6 +205,19 @@ class OrderBySpec:
     count: int = -1
 
 
+SET_OP = {"UNION": 0, "INTERSECT": 1, "MINUS": 2, "UNION ALL": 3}    # NGX_SET_* (UNION: DISTINCT)
+
+
+class SetPlanC(ctypes.Structure):
+    _fields_ = [("op", c_i32)]
+
+
+class SetResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("nrows", c_u64), ("cells", P(Cell)),
+                ("strings", ctypes.c_void_p), ("strings_len", c_u64), ("left_rows", c_u64), ("right_rows", c_u64),
+                ("device_ms", c_dbl)]
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -240,6 +253,9 @@ SIGNATURES = {
     "ngx_go_order_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(OrderPlanC), P(P(OrderResultC))]),
     "ngx_order_result_free": (None, [P(OrderResultC)]),
     "ngx_go_group_order_by": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GroupPlanC), P(OrderPlanC), P(P(OrderResultC))]),
+    "ngx_set_op": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GoResultC), P(SetPlanC), P(P(SetResultC))]),
+    "ngx_go_set": (c_i32, [ctypes.c_void_p, P(GoPlan), P(GoPlan), P(SetPlanC), P(P(SetResultC))]),
+    "ngx_set_result_free": (None, [P(SetResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
     "ngx_kernel_stats": (c_i32, [ctypes.c_void_p, P(P(KernelStat)), P(c_i32)]),
     "ngx_set_flag": (c_i32, [ctypes.c_void_p, ctypes.c_char_p, c_i64]),
@@ -411,6 +427,7 @@ class Engine:
     device_group_by = True                     # go(..., group_by=...) groups a device-resident result (pipeline.py)
     device_order_by = True                     # go(..., order_by=...) selects a device-resident result's top rows
     device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
+    device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -752,6 +769,42 @@ class Engine:
 
     def _group_order_by(self, go_out, group: GroupBySpec, order: OrderBySpec, res: GoResult):
         self._order_by(go_out, order, res, group=group)
+
+    def go_set(self, space: int, left: Union[str, ngql.GoSentence], right: Union[str, ngql.GoSentence], op: str,
+               pushdown: bool = True, now_sec: int = 0, compact: bool = True, rows: bool = True) -> GoResult:
+        """`left <op> right` with op "UNION" (DISTINCT), "INTERSECT" or "MINUS": both GOs run with their results
+        left in HBM and the set operator runs there too (ngx_go_set); only the output rows cross. GoResult.rows /
+        nrows / col_types are the output's, device_ms the set operator's, go_nrows the two inputs' rows together.
+        NGX_E_UNSUPPORTED of the set stage ("set op: ...") comes back as a result with that code and the reason
+        (the caller runs the host path); a traversal's own refusal raises, as go() does. rows=False skips decoding
+        the cells into Python tuples: GoResult.digests is then the cells' value words as an int64 array of shape
+        (nrows, ncols) (integers, double bits, string offsets)."""
+        keep = [self.prepare_go(space, s, pushdown=pushdown, now_sec=now_sec, on_device=True, yield_only=True,
+                                compact=compact) for s in (left, right)]
+        plan = SetPlanC(SET_OP[op])
+        out = P(SetResultC)()
+        rc = self.L.ngx_go_set(self.h, ctypes.byref(keep[0].plan), ctypes.byref(keep[1].plan), ctypes.byref(plan),
+                               ctypes.byref(out))
+        try:
+            err = self.L.ngx_last_error(self.h).decode() if rc else ""
+            if rc in (E_DEVICE, E_UNSUPPORTED) and not err.startswith("set op:"):
+                raise EngineError(rc, err)
+            if rc == E_DEVICE:
+                raise EngineError(rc, err)
+            o = out.contents
+            res = GoResult(ok=rc == 0, error=err, code=rc, col_types=o.col_types[:o.ncols] if o.ncols else [], rows=[],
+                           nrows=o.nrows, device_ms=o.device_ms, go_nrows=o.left_rows + o.right_rows)
+            if rc == 0 and rows:
+                strings = ctypes.string_at(o.strings, o.strings_len) if o.strings_len else b""
+                res.rows = _cells(o.cells, o.nrows, o.ncols, strings)
+            elif rc == 0:
+                raw = ctypes.string_at(ctypes.cast(o.cells, ctypes.c_void_p).value, o.nrows * o.ncols * ctypes.sizeof(Cell)) \
+                    if o.nrows and o.ncols else b""
+                cell = np.dtype([("kind", "<i4"), ("len", "<i4"), ("v", "<i8")])
+                res.digests = np.frombuffer(raw, dtype=cell)["v"].reshape(o.nrows, o.ncols).copy()
+            return res
+        finally:
+            self.L.ngx_set_result_free(out)
 
     def go_batch(self, prepared: Sequence["PreparedGo"], digests: bool = False):
         """Run prepared GO plans back to back in one native call (ngx_go_batch): per query (code, result

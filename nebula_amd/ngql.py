@@ -725,3 +725,63 @@ def parse_limit(src: str) -> LimitSentence:
         s = LimitSentence(a, integer())
     p.expect("eof")
     return s
+
+
+# ----------------------------------------------------------------------------- set sentences
+# set_sentence (parser.yy:1316-1331): piped sentences joined by UNION [ALL | DISTINCT], INTERSECT and MINUS, one
+# priority, left-associative, looser than `|`; parentheses nest a set sentence as a traverse sentence. A bare UNION
+# is DISTINCT (parser.yy:1319-1323 call setDistinct()).
+SET_OPS = ("UNION ALL", "UNION", "INTERSECT", "MINUS")
+
+
+def split_set(src: str) -> Tuple[List[str], List[str]]:
+    """(operands, operators) of a set sentence, split at the operator keywords outside quotes and parentheses:
+    n + 1 operand texts (piped sentences) and n operators out of SET_OPS, "UNION" meaning UNION DISTINCT. No
+    operator: ([src], []). An operand without text is a SyntaxError, as in the grammar."""
+    def word_at(i):
+        m = re.match(r"[A-Za-z_][A-Za-z_0-9]*", src[i:])
+        return m.group(0) if m else ""
+    operands, ops, depth, quote, start, i = [], [], 0, None, 0, 0
+    while i < len(src):
+        ch = src[i]
+        if quote:
+            if ch == "\\":
+                i += 1
+            elif ch == quote:
+                quote = None
+        elif ch in "\"'":
+            quote = ch
+        elif ch == "(":
+            depth += 1
+        elif ch == ")":
+            depth -= 1
+        elif depth == 0 and (ch.isalpha() or ch == "_"):
+            w = word_at(i)
+            prev = src[i - 1] if i else " "
+            if w.upper() in ("UNION", "INTERSECT", "MINUS") and not (prev.isalnum() or prev in "_.$@"):
+                op, end = w.upper(), i + len(w)
+                if op == "UNION":
+                    m = re.match(r"\s+(ALL|DISTINCT)\b", src[end:], re.I)
+                    if m:
+                        end += m.end()
+                        if m.group(1).upper() == "ALL":
+                            op = "UNION ALL"
+                operands.append(src[start:i])
+                ops.append(op)
+                start = i = end
+                continue
+            i += max(len(w), 1)
+            continue
+        i += 1
+    operands.append(src[start:])
+    if ops and any(not o.strip() for o in operands):
+        raise SyntaxError("syntax error near `%s'" % ops[0])
+    return operands, ops
+
+
+def is_set(src: str) -> bool:
+    """The text holds a set operator outside quotes and parentheses."""
+    try:
+        return bool(split_set(src)[1])
+    except SyntaxError:
+        return True

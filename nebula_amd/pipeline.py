@@ -18,6 +18,9 @@ library, include/nebula_gn.h ngx_go with input_* set):
     the caller opts in with order_limit=True.
   - A head `GO | GROUP BY | [ORDER BY |] LIMIT` runs in one device call where the backend has it
     (ngx_go_group_order_by; Pipeline._go_group_order_by), also under order_limit=True.
+  - SetExecutor (src/graph/SetExecutor.cpp): `A UNION [ALL | DISTINCT] B`, `A INTERSECT B`, `A MINUS B` over
+    piped sentences (nebula_amd/setop.py), when the caller opts in with set_ops=True; two plain GO operands run
+    with the operator in one device call where the backend has it (ngx_go_set; Pipeline._go_set).
 GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
 default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
@@ -27,7 +30,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-from . import groupby, ngql, orderby
+from . import groupby, ngql, orderby, setop
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
 _KIND_TYPE = {"bool": T_BOOL, "int": T_INT, "id": T_INT, "timestamp": T_INT, "float": T_DOUBLE,
@@ -134,14 +137,21 @@ class Pipeline:
     """Runs nGQL text made of GO sentences, pipes, parentheses, `$v = ...' and `;'."""
 
     def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
-                 order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True, **go_kw):
-        """device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device.
+                 order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
+                 set_ops: bool = False, device_set_op: bool = True, **go_kw):
+        """set_ops=True: UNION / INTERSECT / MINUS sentences run (off by default, as order_limit is: they are
+        refused like every sentence outside this path); device_set_op=False: two plain GO operands are delivered
+        and combined on the host even where the backend could do it in HBM.
+        device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device.
         order_limit=True: ORDER BY and LIMIT sentences run (off by default: they are refused like every
         sentence outside this path); device_order_by=False: `GO | ORDER BY | LIMIT` and `GO | LIMIT` order
         and cut on the host even where the backend could select the rows on the device.
         device_group_order=False: `GO | GROUP BY | [ORDER BY |] LIMIT` groups on the device and orders the group
         rows on the host, even where the backend could do both in one call (it takes all three switches on)."""
         self.device_group_order = device_group_order
+        self.set_ops = set_ops
+        self.device_set_op = device_set_op
+        self.set_fallbacks = 0                                    # device set calls refused after both traversals ran
         self.device_group_by = device_group_by
         self.order_limit = order_limit
         self.device_order_by = device_order_by
@@ -403,8 +413,95 @@ class Pipeline:
             return Outcome(False, str(e), list(inp.names) if inp is not None else [])
         return Outcome(True, "", names, types, rows)
 
+    def _set_spec(self, left_text: str, right_text: str, op: str):
+        """(left GoSentence, right GoSentence) when `GO <op> GO` can run on the device (ngx_go_set): two plain GOs
+        as in _device_spec with as many columns as each other, and an operator with a kernel. None: the host
+        path decides (and reports any error)."""
+        if op == "UNION ALL":
+            return None
+        try:
+            pair = []
+            for text in (left_text, right_text):
+                if len(_split(text, "|")) > 1 or not text.strip().upper().startswith("GO"):
+                    return None
+                s = ngql.parse_go(text)
+                if s.from_type or s.distinct or not s.yields:
+                    return None
+                for y in s.yields:
+                    if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
+                            any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
+                        return None
+                pair.append(s)
+            if len(pair[0].yields) != len(pair[1].yields):
+                return None
+            return pair
+        except (SyntaxError, ValueError):
+            return None
+
+    def _go_set(self, left_text: str, right_text: str, op: str) -> Optional[Outcome]:
+        """`GO <op> GO` with both traversals and the operator on the device; None when the host path has to run
+        (after a "set op: ..." refusal that costs the two traversals once more: set_fallbacks counts those)."""
+        pair = self._set_spec(left_text, right_text, op)
+        if pair is None:
+            return None
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            r = self.backend.go_set(self.space, pair[0], pair[1], op, **kw)
+        except RuntimeError as e:
+            if getattr(e, "code", 0) == -1002:                    # a device-resident GO itself: the plain path decides
+                return None
+            raise
+        if not r.ok:                                              # a refusal, or a side's own error: the host path words it
+            if r.code == -1002 and r.error.startswith("set op:"):
+                self.set_fallbacks += 1
+            return None
+        names = pair[0].column_names(self.edge_names)
+        return Outcome(True, "", names, Interim.from_result(names, r.col_types, r.rows).types, list(r.rows))
+
+    def _set(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """A set sentence (parser.yy set_sentence): piped sentences folded from the left by SetExecutor."""
+        try:
+            operands, ops = ngql.split_set(text)
+        except SyntaxError as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        if not ops:
+            return self._piped(text, inp)
+        if inp is not None:                                       # SetExecutor::feedResult, SetExecutor.cpp:111-114
+            return Outcome(False, "Set operation not support input yet.")
+        acc = None
+        if self.device_set_op and getattr(self.backend, "device_set_op", False):
+            acc = self._go_set(_unwrap(operands[0]), _unwrap(operands[1]), ops[0])
+        first = 1 if acc is not None else 0
+        if acc is None:
+            acc = self._operand(operands[0])
+        for op, operand in list(zip(ops, operands[1:]))[first:]:
+            right = self._operand(operand)
+            if not acc.ok:                                        # both sides ran; the left's error is reported first
+                acc = Outcome(False, "left subquery has error: " + acc.error, acc.names)
+                continue
+            if not right.ok:
+                acc = Outcome(False, "right subquery has error: " + right.error, acc.names)
+                continue
+            li = Interim.from_result(acc.names, acc.col_types, acc.rows)
+            ri = Interim.from_result(right.names, right.col_types, right.rows)
+            try:
+                names, types, rows = setop.apply(op, li.names, li.types, li.rows, ri.names, ri.types, ri.rows)
+            except setop.SetError as e:
+                return Outcome(False, str(e), list(acc.names))
+            acc = Outcome(True, "", names, types, rows)
+        return acc
+
+    def _operand(self, text: str) -> Outcome:
+        """One operand of a set sentence: a piped sentence, or a parenthesised set sentence."""
+        body = _unwrap(text)
+        return self._set(body, None) if ngql.is_set(body) else self._piped(text, None)
+
     def _piped(self, text: str, inp: Optional[Interim]) -> Outcome:
         parts = _split(text, "|")
+        if self.set_ops:                                          # PipeExecutor::prepare, PipeExecutor.cpp:101-106
+            for part in parts[1:]:
+                if ngql.is_set(_unwrap(part)):
+                    return Outcome(False, "SyntaxError: Set op not support input.")
         if self.order_limit:                                      # the reference parses the whole text first
             for part in parts:
                 body = _unwrap(part)
@@ -465,8 +562,10 @@ class Pipeline:
                     if not out.ok:
                         return out
                     continue
-            if len(_split(body, "|")) > 1:
-                out = self._piped(body, cur)                      # ( set_sentence ) as a traverse sentence
+            if self.set_ops and ngql.is_set(body):
+                out = self._set(body, cur)                        # ( set_sentence ) as a traverse sentence
+            elif len(_split(body, "|")) > 1:
+                out = self._piped(body, cur)                      # ( piped ) as a traverse sentence
             elif body.upper().startswith("YIELD") and cur is None:
                 out = self._yield_constant(body)
             elif ngql.is_group_by(body):
@@ -496,7 +595,7 @@ class Pipeline:
                 head, eq, rest = stmt.partition("=")
                 if eq and head.strip()[1:].isidentifier():
                     var, stmt = head.strip()[1:], rest.strip()
-            out = self._piped(stmt, None)
+            out = self._set(stmt, None) if self.set_ops else self._piped(stmt, None)
             if not out.ok:
                 return out
             if var is not None:
@@ -505,6 +604,8 @@ class Pipeline:
 
 
 def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
-        order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True, **go_kw) -> Outcome:
+        order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
+        set_ops: bool = False, device_set_op: bool = True, **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
-                    device_order_by=device_order_by, device_group_order=device_group_order, **go_kw).run(text)
+                    device_order_by=device_order_by, device_group_order=device_group_order, set_ops=set_ops,
+                    device_set_op=device_set_op, **go_kw).run(text)
