@@ -620,6 +620,56 @@ int32_t ngx_go_set(ngx_ctx* ctx, const ngx_go_plan* left, const ngx_go_plan* rig
                    ngx_set_result** out);
 void ngx_set_result_free(ngx_set_result* r);
 
+/* ---------------------------------------------------------------- FIND SHORTEST PATH
+ * `FIND SHORTEST PATH FROM <vids> TO <vids> OVER <edges> [REVERSELY] [UPTO n STEPS]` (FindPathExecutor,
+ * src/graph/FindPathExecutor.cpp) searched in HBM: breadth-first levels from the sources over the sentence's edge
+ * types and from the targets over the opposite ones, one 64-bit set of targets per row on the to side, meeting as
+ * the reference's steps do (step k: paths of 2k - 1 edges, then of 2k; lengths above `upto` never), DESIGN §7.8.
+ * The answer is the path DAG: every edge that lies on a shortest path from a nearest source to a target found,
+ * with the set of those targets (bit j = to[j]). For target j the paths are all walks over its edges from a
+ * source to it (nebula_amd/findpath.py paths_from_dag). Edge order is not fixed.
+ * Refused with NGX_E_UNSUPPORTED and a text starting "find path:" (the caller runs the host restatement,
+ * nebula_amd/findpath.py): ALL and NOLOOP, BIDIRECT, more than 64 targets, a vid listed twice, a vid on both
+ * sides, upto outside 1 .. 500, world > 1, a TTL edge schema or max_edge_returned_per_vertex set, edges with empty
+ * or unreadable values, and more path-DAG edges than flag "path_rows_max" (default 2^20, 1 .. 2^24). All but the
+ * last are refused before any level is expanded.
+ * Flags (read-only): "find_path_device" calls answered on the device, "find_path_levels" levels expanded and
+ * "find_path_edges" path-DAG edges returned by them, "find_path_loop_flushes" LDS buffer flushes inside a sweep's
+ * edge loop. ngx_kernel_stats: launch groups "path_expand", "path_settle", "path_meet", "path_sweep". */
+#define NGX_PATH_SHORTEST 0
+#define NGX_PATH_ALL 1
+#define NGX_PATH_NOLOOP 2
+typedef struct {
+    int32_t space;
+    int32_t kind;                      /* NGX_PATH_* */
+    uint64_t nfrom;
+    const int64_t* from;
+    uint64_t nto;
+    const int64_t* to;
+    int32_t nover;
+    const char* const* over_names;
+    int32_t over_all;
+    int32_t direction;                 /* NGX_DIR_* */
+    uint32_t upto;
+} ngx_path_plan;
+typedef struct {
+    int32_t code;
+    int32_t nedge_names;               /* the OVER list resolved (OVER *: every edge of the space, schema order) */
+    const char* const* edge_names;
+    const int32_t* edge_types;         /* their (positive) types */
+    uint64_t nedges;                   /* path-DAG edges: src -> dst in path orientation */
+    const int64_t* src;
+    const int64_t* dst;
+    const int32_t* type;               /* signed, as the path prints it */
+    const int64_t* rank;
+    const uint64_t* mask;              /* bit j: the edge lies on a shortest path to to[j] */
+    uint64_t found;                    /* bit j: to[j] was reached */
+    int32_t levels;                    /* levels expanded, both sides */
+    double device_ms;                  /* HIP-event time, first clear to the last edge */
+} ngx_path_result;
+int32_t ngx_find_path(ngx_ctx* ctx, const ngx_path_plan* plan, ngx_path_result** out);
+void ngx_path_result_free(ngx_path_result* r);
+
 /* ---------------------------------------------------------------- measurement hooks */
 /* Per-kernel device times of the last ngx_go (HIP events on the engine stream), for bench.py. */
 typedef struct {

@@ -572,6 +572,66 @@ int launchSetBuild(const SetArgs& a, int side, hipStream_t s);
 // every row of `side` looks its tuple up. kSetMinus keeps the rows not found; kSetIntersect those whose ticket
 // (atomicAdd on taken[slot]) is below count[slot]; kSetUnionDistinct the rows that lead their slot (and NaN rows)
 int launchSetProbe(const SetArgs& a, int side, hipStream_t s);
+// FIND SHORTEST PATH over breadth-first levels (findpath.hip; ngx_find_path). A side (0: from the sources over the
+// sentence's types, 1: from the targets over the opposite ones) keeps per row a 64-bit set: on the to side bit j is
+// target j, on the from side bit 0 is "a source". A level is the compacted list of (row, the bits that reached the
+// row at exactly that distance). Kernel boundaries order every hand-off; inside a kernel rows are shared through
+// atomicOr only.
+constexpr uint32_t kPathBuf = 1024;                 // path-DAG edges a workgroup collects in LDS before it reserves output space
+constexpr uint32_t kPathGridMax = 2048;
+struct PathEdge {                                   // one edge of the path DAG, in path orientation (src nearer the sources)
+    int64_t src, dst, rank;
+    uint64_t mask;                                  // the targets whose shortest paths use it
+    int32_t type;                                   // signed, as the path prints it
+    int32_t pad;
+};
+struct PathState {
+    uint64_t touched[2];                            // rows an expansion reached first, per side
+    uint64_t nLevel[2];                             // rows of the level a settle wrote, per side
+    uint64_t found[2];                              // targets met by this step's odd / even meet
+    uint64_t edges;                                 // path-DAG edges appended (may pass the capacity: nothing is written there)
+    uint32_t loopFlushes;                           // LDS buffer flushes inside a sweep's edge loop
+    uint32_t err;                                   // a list past its capacity: cannot be
+};
+// level 0 of a side: every looked-up row (kNoRow: the vid has no vertex) gets bit `firstBit + (perEntry ? i : 0)`
+int launchPathSeed(const uint32_t* rowsIn, uint64_t n, int perEntry, uint64_t* seen, uint64_t* newD, uint8_t* lvl,
+                   uint32_t* outRows, uint64_t* outMask, uint64_t* count, hipStream_t s);
+// every edge of a level's rows ORs the row's bits into inc[dst]; the lane whose OR found inc[dst] == 0 lists dst
+int launchPathExpand(const uint32_t* rows, const uint64_t* masks, uint64_t n, const HopSlots& hs, uint64_t* inc, uint32_t* touched,
+                     uint64_t cap, PathState* S, int side, hipStream_t s);
+// after the expansion's ORs are complete: per touched row new = inc & ~seen, seen |= new, inc = 0; rows with new != 0
+// form the next level (newD / lvl: the row's latest level and its bits, for the odd meet)
+int launchPathSettle(const uint32_t* touched, uint64_t n, uint64_t* inc, uint64_t* seen, uint64_t* newD, uint8_t* lvl, uint8_t level,
+                     uint32_t* outRows, uint64_t* outMask, PathState* S, int side, hipStream_t s);
+// even meet: the to side's level-k rows that are the from side's level-k rows too. S->found[1] |= the targets not
+// found before (foundPrev | S->found[0]); keepF / keepT[row] = those bits
+int launchPathMeetEven(const uint32_t* rowsT, const uint64_t* masksT, uint64_t nMax, const uint8_t* fLvl, uint8_t level,
+                       uint64_t foundPrev, uint64_t* keepF, uint64_t* keepT, PathState* S, hipStream_t s);
+struct PathSweepArgs {
+    const uint32_t* rows;                           // a level's rows, a wave per (row, slot)
+    const uint64_t* masks;                          // their own bits; null: every bit (the from side)
+    uint64_t n;
+    HopSlots hs;
+    const int64_t* vid;
+    const uint64_t* keepCur;                        // sweep: the keep masks of the level beyond
+    uint64_t* keepNext;                             // the rows' own keep masks (meet: the from side's)
+    const uint8_t* tLvl;                            // meet: the to side's latest level per row and its bits
+    const uint64_t* tNew;
+    uint64_t* keepT;
+    uint64_t notFound;
+    PathEdge* out;
+    uint64_t cap;
+    PathState* S;
+    uint8_t level;
+    int32_t reverse;                                // to side: an edge row -> dst is the path step dst -> row, type negated
+    uint32_t gridMax;
+};
+// meet == false: an edge into a row whose keepCur shares bits with this row's own mask is a path-DAG edge with those
+// bits, and they join keepNext[row]. meet == true (odd meet): an edge into a row of the to side's level `level`
+// whose bits are not found yet; the bits join keepNext[row], keepT[dst] and S->found[0]
+int launchPathSweep(const PathSweepArgs& a, bool meet, hipStream_t s);
+int launchPathClear(const uint32_t* rows, uint64_t n, uint64_t* arr, hipStream_t s);
+
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

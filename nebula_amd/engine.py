@@ -218,6 +218,20 @@ class SetResultC(ctypes.Structure):
                 ("device_ms", c_dbl)]
 
 
+PATH_KIND = {"SHORTEST": 0, "ALL": 1, "NOLOOP": 2}               # NGX_PATH_*
+
+
+class PathPlanC(ctypes.Structure):
+    _fields_ = [("space", c_i32), ("kind", c_i32), ("nfrom", c_u64), ("from_", P(c_i64)), ("nto", c_u64), ("to", P(c_i64)),
+                ("nover", c_i32), ("over_names", P(ctypes.c_char_p)), ("over_all", c_i32), ("direction", c_i32), ("upto", c_u32)]
+
+
+class PathResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("nedge_names", c_i32), ("edge_names", P(ctypes.c_char_p)), ("edge_types", P(c_i32)),
+                ("nedges", c_u64), ("src", P(c_i64)), ("dst", P(c_i64)), ("type", P(c_i32)), ("rank", P(c_i64)),
+                ("mask", P(c_u64)), ("found", c_u64), ("levels", c_i32), ("device_ms", c_dbl)]
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -256,6 +270,8 @@ SIGNATURES = {
     "ngx_set_op": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GoResultC), P(SetPlanC), P(P(SetResultC))]),
     "ngx_go_set": (c_i32, [ctypes.c_void_p, P(GoPlan), P(GoPlan), P(SetPlanC), P(P(SetResultC))]),
     "ngx_set_result_free": (None, [P(SetResultC)]),
+    "ngx_find_path": (c_i32, [ctypes.c_void_p, P(PathPlanC), P(P(PathResultC))]),
+    "ngx_path_result_free": (None, [P(PathResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
     "ngx_kernel_stats": (c_i32, [ctypes.c_void_p, P(P(KernelStat)), P(c_i32)]),
     "ngx_set_flag": (c_i32, [ctypes.c_void_p, ctypes.c_char_p, c_i64]),
@@ -428,6 +444,7 @@ class Engine:
     device_order_by = True                     # go(..., order_by=...) selects a device-resident result's top rows
     device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
     device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
+    device_find_path = True                    # find_path(space, sentence) searches FIND SHORTEST PATH in HBM
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -478,18 +495,21 @@ class Engine:
 
     def load_csr(self, space: int, vpart, vid, slots):
         """ngx_load_csr: this shard's vertex table (sorted by (part, vid)) and per slot (etype, off, dst,
-        [column arrays of the latest schema's fields]) as int64 / uint64 arrays (datagen.Csr.slots)."""
+        [column arrays of the latest schema's fields][, ranks]) as int64 / uint64 arrays (datagen.Csr.slots); without
+        the fifth entry every edge has rank 0."""
         vpart = np.ascontiguousarray(vpart, dtype=np.int32)
         vid = np.ascontiguousarray(vid, dtype=np.int64)
         keep = [vpart, vid]
         cs = (CsrSlotC * max(1, len(slots)))()
-        for k, (etype, off, dst, cols) in enumerate(slots):
+        for k, slot in enumerate(slots):
+            etype, off, dst, cols = slot[:4]
             off = np.ascontiguousarray(off, dtype=np.uint64)
             dst = np.ascontiguousarray(dst, dtype=np.int64)
             cols = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
             ptrs = (ctypes.c_void_p * max(1, len(cols)))(*[c.ctypes.data for c in cols])
-            keep += [off, dst, cols, ptrs]
-            cs[k] = CsrSlotC(int(etype), off.ctypes.data, dst.ctypes.data, None, len(cols),
+            rank = np.ascontiguousarray(slot[4], dtype=np.int64) if len(slot) > 4 and slot[4] is not None else None
+            keep += [off, dst, cols, ptrs, rank]
+            cs[k] = CsrSlotC(int(etype), off.ctypes.data, dst.ctypes.data, rank.ctypes.data if rank is not None else None, len(cols),
                              ctypes.cast(ptrs, ctypes.c_void_p))
         sh = CsrShardC(len(vid), vpart.ctypes.data, vid.ctypes.data, len(slots), cs)
         self._check(self.L.ngx_load_csr(self.h, space, ctypes.byref(sh)), "load_csr")
@@ -805,6 +825,54 @@ class Engine:
             return res
         finally:
             self.L.ngx_set_result_free(out)
+
+    def find_path(self, space: int, s: Union[str, ngql.FindPathSentence], from_vids: Optional[Sequence[int]] = None,
+                  to_vids: Optional[Sequence[int]] = None, rows: bool = True) -> GoResult:
+        """`FIND SHORTEST PATH ...` searched in HBM (ngx_find_path): the levels, the meets and the sweeps run on the
+        device, only the path DAG's edges cross, and the paths are enumerated from them here (findpath.paths_from_dag).
+        from_vids / to_vids: the vids of a sentence whose FROM / TO read `$-` or a variable (findpath.setup_vids).
+        GoResult.rows are one ("path", text) cell each, in no fixed order; nrows their number; go_nrows the path-DAG
+        edges, hop_frontier [levels expanded], device_ms the call's. NGX_E_UNSUPPORTED with a text starting
+        "find path:" comes back as a result with that code (the caller runs the host restatement); any other failure
+        as a result with its code and text too. rows=False skips the enumeration (GoResult.dev_cols keeps the edge
+        arrays src, dst, type, rank, mask)."""
+        from . import findpath
+        if isinstance(s, str):
+            s = ngql.parse_find_path(s)
+        fv = list(s.from_vids if from_vids is None else from_vids)
+        tv = list(s.to_vids if to_vids is None else to_vids)
+        if (from_vids is None and s.from_type) or (to_vids is None and s.to_type):
+            raise EngineError(E_BAD_ARGUMENT, "find_path: the sentence reads $- or a variable; pass from_vids / to_vids")
+        keys = [a or n for n, a in s.over]
+        if len(set(keys)) != len(keys):                           # prepareOver's `edge alias(...) was dup`: the host words it
+            return GoResult(ok=False, error="find path: an edge alias listed twice", code=E_UNSUPPORTED, col_types=[], rows=[])
+        fa, ta = np.array(fv, dtype=np.int64), np.array(tv, dtype=np.int64)
+        names = (ctypes.c_char_p * max(1, len(s.over)))(*[n.encode() for n, _ in s.over])
+        plan = PathPlanC(space, PATH_KIND[s.kind], len(fa), fa.ctypes.data_as(P(c_i64)), len(ta), ta.ctypes.data_as(P(c_i64)),
+                         len(s.over), names, 1 if s.over_all else 0, s.direction, min(int(s.upto), 2 ** 32 - 1))
+        out = P(PathResultC)()
+        rc = self.L.ngx_find_path(self.h, ctypes.byref(plan), ctypes.byref(out))
+        try:
+            err = self.L.ngx_last_error(self.h).decode() if rc else ""
+            if rc == E_DEVICE:
+                raise EngineError(rc, err)
+            o = out.contents
+            res = GoResult(ok=rc == 0, error=err, code=rc, col_types=[], rows=[], device_ms=o.device_ms, go_nrows=o.nedges,
+                           hop_frontier=[o.levels])
+            if rc:
+                return res
+            m = o.nedges
+            cols = (_arr(o.src, m, np.int64), _arr(o.dst, m, np.int64), _arr(o.type, m, np.int32), _arr(o.rank, m, np.int64),
+                    _arr(o.mask, m, np.uint64))
+            res.dev_cols = list(cols)
+            if rows:
+                type_names = {o.edge_types[i]: o.edge_names[i].decode() for i in range(o.nedge_names)}
+                res.rows = [(("path", t),) for t in findpath.paths_from_dag(fv, tv, *cols, type_names)]
+                res.nrows = len(res.rows)
+                res.col_types = [findpath.T_PATH] if res.rows else []
+            return res
+        finally:
+            self.L.ngx_path_result_free(out)
 
     def go_batch(self, prepared: Sequence["PreparedGo"], digests: bool = False):
         """Run prepared GO plans back to back in one native call (ngx_go_batch): per query (code, result

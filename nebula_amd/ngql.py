@@ -785,3 +785,104 @@ def is_set(src: str) -> bool:
         return bool(split_set(src)[1])
     except SyntaxError:
         return True
+
+
+# ----------------------------------------------------------------------------- FIND PATH sentence
+# find_path_sentence (parser.yy:946-994): FIND SHORTEST | ALL | NOLOOP PATH from_clause to_clause over_clause
+# [UPTO n STEPS]. FindPathSentence(isShortest, isNoLoop): SHORTEST is (true, true), ALL (false, false), NOLOOP
+# (false, true). FIND, SHORTEST, ALL, NOLOOP, PATH and UPTO are matched as words (_word), not lexed as keywords,
+# so GO texts lex as before.
+PATH_KINDS = ("SHORTEST", "ALL", "NOLOOP")
+
+
+@dataclass
+class FindPathSentence:
+    kind: str = "SHORTEST"
+    from_vids: List[int] = field(default_factory=list)
+    from_type: int = 0                                            # 0 literal vids, 1 $-.col, 2 $var.col (as GoSentence)
+    from_var: str = ""
+    from_col: str = ""
+    to_vids: List[int] = field(default_factory=list)
+    to_type: int = 0
+    to_var: str = ""
+    to_col: str = ""
+    over: List[Tuple[str, str]] = field(default_factory=list)     # (edge name, alias or "")
+    over_all: bool = False
+    direction: int = FORWARD
+    upto: int = 5                                                 # find_path_upto_clause: %empty is StepClause(5)
+
+    @property
+    def shortest(self) -> bool:
+        return self.kind == "SHORTEST"
+
+    @property
+    def no_loop(self) -> bool:
+        return self.kind in ("SHORTEST", "NOLOOP")
+
+
+def is_find_path(src: str) -> bool:
+    return re.match(r"\s*FIND\b", src, re.I) is not None
+
+
+def _vertices(p: Parser):
+    """vid_list | vid_ref_expression (from_clause / to_clause): (vids, type, var, col)."""
+    t = p.peek()
+    if t.kind == "ref" and t.text == "$-" or t.kind == "var":
+        p.take()
+        p.expect("op", ".")
+        col = "*" if p.accept("op", "*") else p.label()
+        return ([], 1, "", col) if t.kind == "ref" else ([], 2, t.text[1:], col)
+    vids = []
+    while True:
+        if p.peek().kind in ("ref", "var"):
+            raise SyntaxError("FROM / TO accept vids, $-.col or $var.col")
+        e = p.primary() if p.is_op("-") or p.is_op("+") else p.base()
+        if isinstance(e, Unary) and e.op == UNARY_OPS["+"]:
+            e = e.operand
+        v = eval_const(e)
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise SyntaxError("Vertex ID should be of type integer")
+        vids.append(v)
+        if not p.accept("op", ","):
+            return vids, 0, "", ""
+
+
+def parse_find_path(src: str) -> FindPathSentence:
+    p = Parser(src)
+    if _word(p, "FIND") is None:
+        raise SyntaxError(f"expected FIND, got {p.peek().text!r}")
+    kind = _word(p, *PATH_KINDS)
+    if kind is None:
+        raise SyntaxError(f"expected SHORTEST, ALL or NOLOOP, got {p.peek().text!r}")
+    if _word(p, "PATH") is None:
+        raise SyntaxError(f"expected PATH, got {p.peek().text!r}")
+    s = FindPathSentence(kind=kind)
+    p.expect("kw", "FROM")
+    s.from_vids, s.from_type, s.from_var, s.from_col = _vertices(p)
+    p.expect("kw", "TO")
+    s.to_vids, s.to_type, s.to_var, s.to_col = _vertices(p)
+    p.expect("kw", "OVER")
+    if p.accept("op", "*"):
+        s.over_all = True
+    else:
+        while True:
+            name = p.label()
+            alias = p.label() if p.accept("kw", "AS") else ""
+            s.over.append((name, alias))
+            if not p.accept("op", ","):
+                break
+    if p.accept("kw", "REVERSELY"):
+        s.direction = REVERSELY
+    elif p.accept("kw", "BIDIRECT"):
+        s.direction = BIDIRECT
+    if _word(p, "UPTO") is not None:
+        t = p.peek()
+        if t.kind not in ("int", "hex"):
+            raise SyntaxError(f"expected an integer, got {t.text!r}")
+        p.take()
+        s.upto = int(t.text, 0)
+        if s.upto > (1 << 63) - 1:
+            raise SyntaxError("integer out of range")
+        p.expect("kw", "STEPS")
+    p.expect("eof")
+    return s

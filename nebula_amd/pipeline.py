@@ -21,6 +21,10 @@ library, include/nebula_gn.h ngx_go with input_* set):
   - SetExecutor (src/graph/SetExecutor.cpp): `A UNION [ALL | DISTINCT] B`, `A INTERSECT B`, `A MINUS B` over
     piped sentences (nebula_amd/setop.py), when the caller opts in with set_ops=True; two plain GO operands run
     with the operator in one device call where the backend has it (ngx_go_set; Pipeline._go_set).
+  - FindPathExecutor (src/graph/FindPathExecutor.cpp): `FIND SHORTEST | ALL | NOLOOP PATH FROM ... TO ... OVER ...
+    [UPTO n STEPS]` (nebula_amd/findpath.py), when the caller opts in with find_path=True; FIND SHORTEST PATH runs
+    in one device call where the backend has it (ngx_find_path; Pipeline._find_path). It hands no result on: a
+    sentence piped behind it runs without input.
 GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
 default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
@@ -30,7 +34,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-from . import groupby, ngql, orderby, setop
+from . import findpath, groupby, ngql, orderby, setop
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
 _KIND_TYPE = {"bool": T_BOOL, "int": T_INT, "id": T_INT, "timestamp": T_INT, "float": T_DOUBLE,
@@ -138,8 +142,12 @@ class Pipeline:
 
     def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
                  order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
-                 set_ops: bool = False, device_set_op: bool = True, **go_kw):
-        """set_ops=True: UNION / INTERSECT / MINUS sentences run (off by default, as order_limit is: they are
+                 set_ops: bool = False, device_set_op: bool = True, find_path: bool = False,
+                 device_find_path: bool = True, **go_kw):
+        """find_path=True: FIND PATH sentences run (off by default, as order_limit and set_ops are);
+        device_find_path=False: every FIND PATH sentence takes the host restatement (findpath.py) even where the
+        backend could search in HBM. find_path_fallbacks counts the device calls refused with "find path: ...".
+        set_ops=True: UNION / INTERSECT / MINUS sentences run (off by default, as order_limit is: they are
         refused like every sentence outside this path); device_set_op=False: two plain GO operands are delivered
         and combined on the host even where the backend could do it in HBM.
         device_group_by=False: `GO | GROUP BY` groups on the host even where the backend could on the device.
@@ -152,6 +160,10 @@ class Pipeline:
         self.set_ops = set_ops
         self.device_set_op = device_set_op
         self.set_fallbacks = 0                                    # device set calls refused after both traversals ran
+        self.find_path = find_path
+        self.device_find_path = device_find_path
+        self.find_path_fallbacks = 0
+        self.find_path_refusal = ""                               # the last refusal's text
         self.device_group_by = device_group_by
         self.order_limit = order_limit
         self.device_order_by = device_order_by
@@ -491,6 +503,29 @@ class Pipeline:
             acc = Outcome(True, "", names, types, rows)
         return acc
 
+    def _find_path(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """A FIND PATH sentence: on the device where the backend has it and takes the sentence, else
+        FindPathExecutor restated on the host (findpath.run)."""
+        try:
+            s = ngql.parse_find_path(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            if self.device_find_path and getattr(self.backend, "device_find_path", False):
+                from_vids, to_vids = findpath.setup_vids(s, inp, self.variables)
+                r = self.backend.find_path(self.space, s, from_vids, to_vids)
+                if r.ok:
+                    return Outcome(True, "", ["_path_"], [findpath.T_PATH] if r.rows else [], list(r.rows))
+                if r.code != -1002 or not r.error.startswith("find path:"):
+                    return Outcome(False, r.error, ["_path_"])
+                self.find_path_fallbacks += 1
+                self.find_path_refusal = r.error
+            names, types, rows = findpath.run(self.backend, self.space, s, inp, self.variables, self.edge_names, **kw)
+        except findpath.FindPathError as e:
+            return Outcome(False, str(e), ["_path_"])
+        return Outcome(True, "", names, types, rows)
+
     def _operand(self, text: str) -> Outcome:
         """One operand of a set sentence: a piped sentence, or a parenthesised set sentence."""
         body = _unwrap(text)
@@ -574,6 +609,12 @@ class Pipeline:
                 out = self._order_by(body, cur)
             elif self.order_limit and ngql.is_limit(body):
                 out = self._limit(body, cur)
+            elif self.find_path and ngql.is_find_path(body):
+                out = self._find_path(body, cur)
+                if not out.ok:
+                    return out
+                cur = None                                        # FindPathExecutor never calls onResult_
+                continue
             else:
                 if not body.upper().startswith("GO"):
                     raise PipelineError("only GO sentences run in this path: " + body[:40])
@@ -605,7 +646,8 @@ class Pipeline:
 
 def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
         order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
-        set_ops: bool = False, device_set_op: bool = True, **go_kw) -> Outcome:
+        set_ops: bool = False, device_set_op: bool = True, find_path: bool = False, device_find_path: bool = True,
+        **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
                     device_order_by=device_order_by, device_group_order=device_group_order, set_ops=set_ops,
-                    device_set_op=device_set_op, **go_kw).run(text)
+                    device_set_op=device_set_op, find_path=find_path, device_find_path=device_find_path, **go_kw).run(text)
