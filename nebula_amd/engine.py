@@ -402,6 +402,7 @@ class GoResult:
     order_device_ms: float = 0.0
     order_host_sort_ms: float = 0.0
     ngroups: int = 0                     # group_by + order_by: the groups the window was cut from
+    path_found: int = 0                  # find_path: bit j set when target j was found (ngx_path_result.found)
 
 
 @dataclass
@@ -832,8 +833,8 @@ class Engine:
         device, only the path DAG's edges cross, and the paths are enumerated from them here (findpath.paths_from_dag).
         from_vids / to_vids: the vids of a sentence whose FROM / TO read `$-` or a variable (findpath.setup_vids).
         GoResult.rows are one ("path", text) cell each, in no fixed order; nrows their number; go_nrows the path-DAG
-        edges, hop_frontier [levels expanded], device_ms the call's. NGX_E_UNSUPPORTED with a text starting
-        "find path:" comes back as a result with that code (the caller runs the host restatement); any other failure
+        edges, hop_frontier [levels expanded], path_found the found targets' bits, device_ms the call's.
+        NGX_E_UNSUPPORTED with a text starting "find path:" comes back as a result with that code (the caller runs the host restatement); any other failure
         as a result with its code and text too. rows=False skips the enumeration (GoResult.dev_cols keeps the edge
         arrays src, dst, type, rank, mask)."""
         from . import findpath
@@ -858,7 +859,7 @@ class Engine:
                 raise EngineError(rc, err)
             o = out.contents
             res = GoResult(ok=rc == 0, error=err, code=rc, col_types=[], rows=[], device_ms=o.device_ms, go_nrows=o.nedges,
-                           hop_frontier=[o.levels])
+                           hop_frontier=[o.levels], path_found=int(o.found))
             if rc:
                 return res
             m = o.nedges

@@ -10,45 +10,14 @@ inside the edge loop) and the path_rows_max refusal; 64 targets and 65; a vertex
 (what the per-target seen mask is for); two sources at different distances; an unreachable target; a vid without a
 vertex; a vertex on both sides; poisoned scratch; a GO before and after.
 """
-import numpy as np
 import pytest
 
-from nebula_amd import engine, kvfmt, pipeline
-from tests import fixtures
+from nebula_amd import engine, pipeline
+from tests.pathref import load, refused
 
 pytestmark = pytest.mark.gpu
 
 EDGES = ["e", "f"]
-SCHEMA = [fixtures.SchemaDef(True, 1, "e", [("p0", kvfmt.INT)]), fixtures.SchemaDef(True, 2, "f", [("p0", kvfmt.INT)])]
-_space = [100]
-
-
-def load(e, nv, edges):
-    """edges: (src row, dst row, type, rank). Returns the space."""
-    _space[0] += 1
-    space = _space[0]
-    e.add_space(space, 1)
-    for s in SCHEMA:
-        e.add_schema(space, s.is_edge, s.sid, s.name, s.fields)
-    slots = []
-    for t in sorted({x[2] for x in edges}):
-        for sign in (1, -1):
-            rows = [[] for _ in range(nv)]
-            for a, b, tt, r in edges:
-                if tt == t:
-                    (rows[a] if sign > 0 else rows[b]).append((r, (b if sign > 0 else a) + 1))
-            off, dst, rank = [0], [], []
-            for lst in rows:
-                for r, d in sorted(lst, key=lambda x: (x[0].to_bytes(8, "little"), x[1].to_bytes(8, "little"))):
-                    dst.append(d)
-                    rank.append(r)
-                off.append(len(dst))
-            slots.append((sign * t, np.array(off, np.uint64), np.array(dst, np.int64), [np.zeros(len(dst), np.int64)],
-                          np.array(rank, np.int64)))
-    e.load_csr(space, np.ones(nv, np.int32), np.arange(1, nv + 1, dtype=np.int64), slots)
-    e.commit(space)
-    return space
-
 
 @pytest.fixture(scope="module")
 def eng():
@@ -71,19 +40,6 @@ def both(e, space, q):
     assert host.ok, host.error
     assert dev == sorted(r[0][1] for r in host.rows)
     return dev
-
-
-def refused(e, space, q, reason):
-    """The device call refuses with `reason`; the pipeline answers from the host restatement."""
-    r = e.find_path(space, q)
-    assert not r.ok and r.code == engine.E_UNSUPPORTED and r.error.startswith("find path:") and reason in r.error, r.error
-    before = e.get_flag("find_path_device")
-    p = pipeline.Pipeline(e, space, EDGES, find_path=True)
-    out = p.run(q)
-    assert out.ok and p.find_path_fallbacks == 1 and e.get_flag("find_path_device") == before
-    host = pipeline.run(e, space, q, EDGES, find_path=True, device_find_path=False)
-    assert sorted(out.rows) == sorted(host.rows)
-    return sorted(r[0][1] for r in out.rows)
 
 
 def chain_text(vids, edge="e", rank=0):
