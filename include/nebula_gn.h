@@ -620,6 +620,94 @@ int32_t ngx_go_set(ngx_ctx* ctx, const ngx_go_plan* left, const ngx_go_plan* rig
                    ngx_set_result** out);
 void ngx_set_result_free(ngx_set_result* r);
 
+/* ---------------------------------------------------------------- FETCH PROP ON tags / an edge type */
+/* `FETCH PROP ON <tags> <vids> | $-.col [YIELD ...]` and `FETCH PROP ON <edge> <src> -> <dst>[@rank] | $-.s -> $-.d
+ * [YIELD ...]` with the key lookup and the property gather on the device: replaces FetchVerticesExecutor's
+ * StorageClient::getVertexProps (QueryVertexPropsProcessor) and FetchEdgesExecutor's StorageClient::getEdgeProps
+ * (QueryEdgePropsProcessor) with their processResult loops (src/graph/FetchVerticesExecutor.cpp:322-589,
+ * FetchEdgesExecutor.cpp:303-431). Only the cells and string bytes of the output rows cross PCIe.
+ *
+ * ngx_fetch is the kernel stage. `r` is a result_on_device result of this context that is valid when it is called
+ * (ngx_go_fetch below arranges that; a test may hand it any columns in HBM): key_cols name its columns holding the
+ * vid, or src, dst and rank (rank column -1: rank 0), read in place through dev_cols, dev_col_w and dev_col_const
+ * as ngx_set_op reads them. With r == NULL the keys are the host arrays key_vid (the vid, or src), key_dst and
+ * key_rank of nkeys entries (key_rank NULL with key_cols[2] == -1: rank 0); an NGX_FY_INPUT_COL yield then names
+ * key array 0, 1 or 2.
+ *   NGX_FETCH_VERTEX  per key: part = (uint64)vid % parts + 1, the row through the (part, vid) index, one hit per
+ *                     ON tag. A key is kept when a tag hit or keep_missing is set (the YIELD reads `$-`: "no data
+ *                     and no input prop: no row, else a row of RowReader::getDefaultProp values"). Output columns:
+ *                     the vid (VID), then the yields; a tag the vertex lacks, or a field the row's schema version
+ *                     lacks, gives 0 / 0.0 / false / "". tags_seen: bit t set when some key had a row of tags[t]
+ *                     (the caller builds the no-YIELD column set from it).
+ *   NGX_FETCH_EDGE    per key: the source's row, then a binary search of its adjacency under the stored (KV key)
+ *                     order for (rank, dst), compared at 64 bits. Only found keys are kept. Output columns: src
+ *                     (VID), dst (VID), rank (INT), then the yields.
+ * Output rows keep the order of the keys; the output is sized exactly by a count pass (no row cap).
+ * Prepare-time errors come as NGX_E_QUERY with the reference's text: an unknown tag or edge ("Unknown error(406): "
+ * / "Unknown error(407): ", the text of Status::TagNotFound / EdgeNotFound), "tag(x) was dup", "`tag' is not a prop
+ * of `field'" / "`field' is not a prop of `edge'".
+ * NGX_E_UNSUPPORTED, with a reason in ngx_last_error that starts "fetch:" and decided before any launch, for: a
+ * yield that is no plain prop, key prop or input column, ON * (ntags == 0), more than 8 tags or 16 output columns, a
+ * TTL tag or edge schema, an edge slot holding edges with empty or unreadable values, an UNKNOWN-typed or
+ * non-integer key column (UNKNOWN-typed input columns too), world > 1, 2^31 keys or more. The caller then runs the
+ * host path. `distinct` is carried for the caller: literal keys arrive deduplicated, and ngx_fetch refuses
+ * ("fetch: DISTINCT over device-resident edge keys") only where it would have to deduplicate rows in HBM.
+ *
+ * ngx_go_fetch is the product call: the GO with result_on_device (yield_only and compact_results as the caller
+ * sets them), without DISTINCT or input, then ngx_fetch over its result, then the result freed. The traversal's
+ * error is the call's.
+ * Flags: "fetch_device" (read-only) counts the calls completed on the device; "fetch_grid_max" (0, the default:
+ * built-in 2048, else 1 .. 2048) caps the workgroups of the key and emit kernels (256 keys a workgroup and sweep):
+ * same results under every setting. ngx_kernel_stats: launch groups "fetch_keys", "fetch_scan", "fetch_emit". */
+#define NGX_FETCH_VERTEX 0
+#define NGX_FETCH_EDGE 1
+#define NGX_FY_TAG_PROP 0
+#define NGX_FY_EDGE_PROP 1
+#define NGX_FY_EDGE_KEY 2
+#define NGX_FY_INPUT_COL 3
+#define NGX_EK_SRC 0
+#define NGX_EK_DST 1
+#define NGX_EK_RANK 2
+#define NGX_EK_TYPE 3
+typedef struct {
+    int32_t kind;                      /* NGX_FY_* */
+    int32_t tag;                       /* NGX_FY_TAG_PROP: the tag id (one of the plan's tags) */
+    const char* field;                 /* NGX_FY_TAG_PROP / NGX_FY_EDGE_PROP: the field's name */
+    int32_t key;                       /* NGX_FY_EDGE_KEY: NGX_EK_* */
+    int32_t col;                       /* NGX_FY_INPUT_COL: column of r (r == NULL: key array 0 .. 2) */
+} ngx_fetch_yield;
+typedef struct {
+    int32_t space;
+    int32_t kind;                      /* NGX_FETCH_* */
+    int32_t ntags;                     /* NGX_FETCH_VERTEX: the tag ids in ON order; 0: ON * (refused) */
+    const int32_t* tags;
+    int32_t edge_type;                 /* NGX_FETCH_EDGE: the one edge type (> 0) */
+    int32_t key_cols[3];               /* columns of r: vid | src, dst, rank (-1: rank 0) */
+    uint64_t nkeys;                    /* r == NULL: the host key arrays */
+    const int64_t* key_vid;
+    const int64_t* key_dst;
+    const int64_t* key_rank;
+    int32_t distinct;
+    int32_t keep_missing;              /* NGX_FETCH_VERTEX: a key without data keeps its row (YIELD reads `$-`) */
+    int32_t nyields;
+    const ngx_fetch_yield* yields;
+} ngx_fetch_plan;
+typedef struct {
+    int32_t code;
+    int32_t ncols;
+    const int32_t* col_types;          /* NGX_T_* per column */
+    uint64_t nrows;
+    const ngx_cell* cells;             /* cells[row * ncols + col] */
+    const char* strings;
+    uint64_t strings_len;
+    uint64_t input_rows;               /* keys looked up */
+    uint32_t tags_seen;                /* NGX_FETCH_VERTEX: bit t: some key had a row of tags[t] */
+    double device_ms;                  /* HIP-event time of the call, key upload to the last cell */
+} ngx_fetch_result;
+int32_t ngx_fetch(ngx_ctx* ctx, const ngx_go_result* r, const ngx_fetch_plan* plan, ngx_fetch_result** out);
+int32_t ngx_go_fetch(ngx_ctx* ctx, const ngx_go_plan* go, const ngx_fetch_plan* plan, ngx_fetch_result** out);
+void ngx_fetch_result_free(ngx_fetch_result* r);
+
 /* ---------------------------------------------------------------- FIND SHORTEST PATH
  * `FIND SHORTEST PATH FROM <vids> TO <vids> OVER <edges> [REVERSELY] [UPTO n STEPS]` (FindPathExecutor,
  * src/graph/FindPathExecutor.cpp) searched in HBM: breadth-first levels from the sources over the sentence's edge

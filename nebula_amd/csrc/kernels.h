@@ -54,6 +54,31 @@ __host__ __device__ inline uint64_t vindexHash(int32_t part, int64_t vid) {
     return h ^ (h >> 32);
 }
 
+#ifdef __HIPCC__
+// linear probing, two slots per round trip: both loads issue before either is compared (most keys
+// resolve in the first pair at the index's load factor)
+// Two slots per round trip, each one 16-byte load, both issued before either is examined, and the
+// outcome picked by selects (a probe written with early returns let the compiler split each slot
+// into a row load and a key load behind branches: four dependent loads per probe pair, r04 ISA).
+__device__ __forceinline__ uint4 vindexSlot(const VIndex& idx, uint64_t h) {
+    return reinterpret_cast<const uint4*>(idx.slots)[h];
+}
+__device__ __forceinline__ uint32_t vindexFind(const VIndex& idx, int32_t part, int64_t vid) {
+    uint64_t h = vindexHash(part, vid) & idx.mask;
+    const uint32_t vlo = static_cast<uint32_t>(vid), vhi = static_cast<uint32_t>(static_cast<uint64_t>(vid) >> 32);
+    for (uint64_t probe = 0; probe <= idx.mask; probe += 2) {
+        const uint4 a = vindexSlot(idx, h), b = vindexSlot(idx, (h + 1) & idx.mask);
+        const bool aHit = a.x == vlo && a.y == vhi && a.z == static_cast<uint32_t>(part) && a.w != kNoRow;
+        const bool bHit = b.x == vlo && b.y == vhi && b.z == static_cast<uint32_t>(part) && b.w != kNoRow;
+        const bool done = aHit || a.w == kNoRow || bHit || b.w == kNoRow;   // found, or an empty slot ends the run
+        const uint32_t r = aHit ? a.w : a.w == kNoRow ? kNoRow : bHit ? b.w : kNoRow;
+        if (done) return r;
+        h = (h + 2) & idx.mask;
+    }
+    return kNoRow;
+}
+#endif
+
 // seed hop (n seeds, n * hs.n <= kSeedFuseMax entries): launchSeedFrontierCf below
 constexpr uint64_t kSeedFuseMax = 4096;
 
@@ -631,6 +656,59 @@ struct PathSweepArgs {
 // whose bits are not found yet; the bits join keepNext[row], keepT[dst] and S->found[0]
 int launchPathSweep(const PathSweepArgs& a, bool meet, hipStream_t s);
 int launchPathClear(const uint32_t* rows, uint64_t n, uint64_t* arr, hipStream_t s);
+
+// FETCH PROP ON tags / an edge type over keys in HBM (fetch.hip; ngx_fetch). Keys are read in place at their stored
+// widths, sign-extended (GroupCol, as the set operator reads a result's columns). Three steps, every one a sweep of
+// 256 keys a workgroup and turn:
+//   keys   a thread per key: the vertex row through the (part, vid) index, part = (uint64)vid % nparts + 1; FETCH
+//          on tags: one hit bit per ON tag from DTag::present; FETCH on an edge: a binary search of the source row's
+//          adjacency for (rank, dst) under the stored order. keep = a hit, or keepMissing. The kept keys of each
+//          256-key chunk are counted by ballot / popcount into chunkCount[chunk].
+//   scan   launchScanU64 over the chunk counts: exclusive bases; the total sizes the output exactly.
+//   emit   re-derives a key's place, base[chunk] + its rank among the chunk's kept keys (ballot / popcount), and
+//          writes the row's cells there, so rows keep the order of the keys. Run twice when a yield is a string:
+//          first with lenOut to write each output row's string bytes (scanned into strPre), then for the cells.
+constexpr int kFetchMaxTags = 8;
+constexpr int kFetchMaxCols = 16;
+constexpr uint32_t kFetchGridMax = 2048;            // workgroups (of 256 keys a sweep) of the key and emit kernels
+constexpr uint64_t kFetchNoEdge = ~0ULL;
+enum { kFyTagProp = 0, kFyEdgeProp, kFyKey, kFyEdgeType, kFyInput };
+struct FetchYield {
+    int32_t src;                        // kFy*
+    int32_t a;                          // kFyTagProp: index into the ON tags; kFyKey: 0 vid / src, 1 dst, 2 rank
+    int32_t cell;                       // NGX_CELL_* of the output cell
+    int32_t pad;
+    DCol col;                           // kFyTagProp / kFyEdgeProp: the stored column
+    GroupCol in;                        // kFyInput: the input column (a string: device pointers and lengths)
+    int64_t konst;                      // kFyEdgeType: the type
+};
+struct FetchArgs {
+    uint64_t n;                         // keys
+    int32_t edge;                       // 0: FETCH on tags, 1: on an edge type
+    int32_t nparts;
+    GroupCol key[3];                    // vid | src, dst, rank (hasRank 0: rank 0)
+    int32_t hasRank;
+    int32_t ntags;
+    VIndex vindex;
+    const uint8_t* present[kFetchMaxTags];
+    DSlot slot;                         // edge: the type's out-slot
+    int32_t keepMissing;                // a key without data keeps its row (the yields read the input)
+    int32_t ny;
+    const FetchYield* ys;               // device array
+    uint32_t* row;                      // per key: the vertex row (kNoRow: none)
+    uint64_t* eidx;                     // edge: per key the edge's index in the slot (kFetchNoEdge: none)
+    uint16_t* hits;                     // per key: bit t = the vertex has a row of ON tag t; edge: bit 0 = found; bit 15 = keep
+    uint64_t* chunkCount;               // per 256-key chunk: kept keys
+    const uint64_t* chunkBase;          // exclusive scan of chunkCount (emit)
+    uint32_t* seen;                     // one word: OR of every key's tag hit bits
+    uint64_t* lenOut;                   // emit, length pass: per output row its string bytes; null: the cell pass
+    const uint64_t* strPre;             // cell pass: exclusive scan of the lengths; null: no string yields
+    char* strOut;
+    GroupCell* cells;                   // m * (nkey + ny): nkey = 1 (VertexID) or 3 (src, dst, rank)
+    uint32_t gridMax;                   // most workgroups of a sweep (flag fetch_grid_max); 0: kFetchGridMax
+};
+int launchFetchKeys(const FetchArgs& a, hipStream_t s);
+int launchFetchEmit(const FetchArgs& a, hipStream_t s);
 
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so

@@ -179,29 +179,6 @@ __global__ void k_lookup(const int32_t* qpart, const int64_t* qvid, uint64_t n, 
     out[i] = (lo < V && vpart[lo] == p && vid[lo] == v) ? static_cast<uint32_t>(lo) : kNoRow;
 }
 
-// linear probing, two slots per round trip: both loads issue before either is compared (most keys
-// resolve in the first pair at the index's load factor)
-// Two slots per round trip, each one 16-byte load, both issued before either is examined, and the
-// outcome picked by selects (a probe written with early returns let the compiler split each slot
-// into a row load and a key load behind branches: four dependent loads per probe pair, r04 ISA).
-__device__ __forceinline__ uint4 vindexSlot(const VIndex& idx, uint64_t h) {
-    return reinterpret_cast<const uint4*>(idx.slots)[h];
-}
-__device__ __forceinline__ uint32_t vindexFind(const VIndex& idx, int32_t part, int64_t vid) {
-    uint64_t h = vindexHash(part, vid) & idx.mask;
-    const uint32_t vlo = static_cast<uint32_t>(vid), vhi = static_cast<uint32_t>(static_cast<uint64_t>(vid) >> 32);
-    for (uint64_t probe = 0; probe <= idx.mask; probe += 2) {
-        const uint4 a = vindexSlot(idx, h), b = vindexSlot(idx, (h + 1) & idx.mask);
-        const bool aHit = a.x == vlo && a.y == vhi && a.z == static_cast<uint32_t>(part) && a.w != kNoRow;
-        const bool bHit = b.x == vlo && b.y == vhi && b.z == static_cast<uint32_t>(part) && b.w != kNoRow;
-        const bool done = aHit || a.w == kNoRow || bHit || b.w == kNoRow;   // found, or an empty slot ends the run
-        const uint32_t r = aHit ? a.w : a.w == kNoRow ? kNoRow : bHit ? b.w : kNoRow;
-        if (done) return r;
-        h = (h + 2) & idx.mask;
-    }
-    return kNoRow;
-}
-
 // seed (part, vid) -> vertex row through the commit-time hash index (GetNeighbors requests)
 __global__ void k_index_lookup(const int32_t* qpart, const int64_t* qvid, uint64_t n, VIndex idx, uint32_t* out) {
     uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;

@@ -232,6 +232,48 @@ class PathResultC(ctypes.Structure):
                 ("mask", P(c_u64)), ("found", c_u64), ("levels", c_i32), ("device_ms", c_dbl)]
 
 
+FETCH_VERTEX, FETCH_EDGE = 0, 1                                 # NGX_FETCH_*
+FY_TAG_PROP, FY_EDGE_PROP, FY_EDGE_KEY, FY_INPUT_COL = 0, 1, 2, 3  # NGX_FY_*
+EDGE_KEY = {"_src": 0, "_dst": 1, "_rank": 2, "_type": 3}        # NGX_EK_*
+
+
+class FetchYieldC(ctypes.Structure):
+    _fields_ = [("kind", c_i32), ("tag", c_i32), ("field", ctypes.c_char_p), ("key", c_i32), ("col", c_i32)]
+
+
+class FetchPlanC(ctypes.Structure):
+    _fields_ = [("space", c_i32), ("kind", c_i32), ("ntags", c_i32), ("tags", P(c_i32)), ("edge_type", c_i32),
+                ("key_cols", c_i32 * 3), ("nkeys", c_u64), ("key_vid", P(c_i64)), ("key_dst", P(c_i64)),
+                ("key_rank", P(c_i64)), ("distinct", c_i32), ("keep_missing", c_i32), ("nyields", c_i32),
+                ("yields", P(FetchYieldC))]
+
+
+class FetchResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("nrows", c_u64), ("cells", P(Cell)),
+                ("strings", ctypes.c_void_p), ("strings_len", c_u64), ("input_rows", c_u64), ("tags_seen", c_u32),
+                ("device_ms", c_dbl)]
+
+
+@dataclass
+class FetchSpec:
+    """ngx_fetch_plan of a prepared FETCH sentence, and what fetch.device_rows needs to name, type and trim the
+    device's rows as the host path would (fetch.device_spec builds it from a sentence).
+    yields: (NGX_FY_*, tag id, field, NGX_EK_*, input column); kind -1: an expression the device refuses."""
+    kind: int
+    tags: List[int]
+    edge_type: int
+    key_cols: Tuple[int, int, int]
+    keys: Optional[List[np.ndarray]]                              # host key arrays; None: the keys are a result's columns
+    distinct: bool
+    keep_missing: bool
+    yields: List[Tuple[int, int, str, int, int]]
+    names: List[str]
+    types: List[int]                                              # schema types of every output column (0: from the value)
+    yield_tag: List[int] = field(default_factory=list)            # no YIELD: index into tags of each yield's tag
+    no_yield: bool = False
+    prefix: List[str] = field(default_factory=list)               # the names when nothing comes back
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -270,6 +312,9 @@ SIGNATURES = {
     "ngx_set_op": (c_i32, [ctypes.c_void_p, P(GoResultC), P(GoResultC), P(SetPlanC), P(P(SetResultC))]),
     "ngx_go_set": (c_i32, [ctypes.c_void_p, P(GoPlan), P(GoPlan), P(SetPlanC), P(P(SetResultC))]),
     "ngx_set_result_free": (None, [P(SetResultC)]),
+    "ngx_fetch": (c_i32, [ctypes.c_void_p, P(GoResultC), P(FetchPlanC), P(P(FetchResultC))]),
+    "ngx_go_fetch": (c_i32, [ctypes.c_void_p, P(GoPlan), P(FetchPlanC), P(P(FetchResultC))]),
+    "ngx_fetch_result_free": (None, [P(FetchResultC)]),
     "ngx_find_path": (c_i32, [ctypes.c_void_p, P(PathPlanC), P(P(PathResultC))]),
     "ngx_path_result_free": (None, [P(PathResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
@@ -403,6 +448,7 @@ class GoResult:
     order_host_sort_ms: float = 0.0
     ngroups: int = 0                     # group_by + order_by: the groups the window was cut from
     path_found: int = 0                  # find_path: bit j set when target j was found (ngx_path_result.found)
+    tags_seen: int = 0                   # fetch: bit t set when some key had a row of the plan's tag t
 
 
 @dataclass
@@ -446,6 +492,7 @@ class Engine:
     device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
     device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
     device_find_path = True                    # find_path(space, sentence) searches FIND SHORTEST PATH in HBM
+    device_fetch = True                        # fetch(space, spec) / go_fetch(space, go, spec) look keys up and gather in HBM
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -462,6 +509,8 @@ class Engine:
             raise EngineError(rc, "ngx_open failed (no HIP device or RCCL init failed)")
         self.h = h
         self.rank, self.world = rank, world
+        self._parts: Dict[int, int] = {}                          # what catalog() hands the FETCH executors
+        self._schemas: Dict[int, list] = {}
 
     def close(self):
         if getattr(self, "h", None):
@@ -481,12 +530,22 @@ class Engine:
     # ---- schema + data
     def add_space(self, space: int, num_parts: int):
         self._check(self.L.ngx_add_space(self.h, space, num_parts), "add_space")
+        self._parts[space] = num_parts
 
     def add_schema(self, space, is_edge, sid, name, fields: Sequence[Tuple[str, int]], ver=0, ttl_col="", ttl_dur=0):
         names = (ctypes.c_char_p * max(1, len(fields)))(*[f[0].encode() for f in fields])
         types = (c_i32 * max(1, len(fields)))(*[f[1] for f in fields])
         self._check(self.L.ngx_add_schema(self.h, space, 1 if is_edge else 0, sid, name.encode(), ver, len(fields),
                                           names, types, ttl_col.encode(), ttl_dur), "add_schema")
+        self._schemas.setdefault(space, []).append((bool(is_edge), sid, name, list(fields), ver))
+
+    def catalog(self, space: int):
+        """The space's fetch.Catalog (partition count, latest tag and edge schemas) from what add_space and
+        add_schema were given: what the FETCH executors ask the schema manager."""
+        from . import fetch
+        from types import SimpleNamespace as NS
+        return fetch.Catalog.of(self._parts[space], [NS(is_edge=e, sid=i, name=n, fields=f, ver=v)
+                                                      for e, i, n, f, v in self._schemas.get(space, [])])
 
     def load_kv(self, space: int, keys, koff, vals, voff):
         keys, vals = np.ascontiguousarray(keys, dtype=np.uint8), np.ascontiguousarray(vals, dtype=np.uint8)
@@ -826,6 +885,64 @@ class Engine:
             return res
         finally:
             self.L.ngx_set_result_free(out)
+
+    def _fetch_plan(self, space: int, spec: FetchSpec):
+        """(FetchPlanC, the arrays it points into)"""
+        tags = (c_i32 * max(1, len(spec.tags)))(*spec.tags)
+        ys = (FetchYieldC * max(1, len(spec.yields)))()
+        for i, (kind, tag, fld, key, col) in enumerate(spec.yields):
+            ys[i].kind, ys[i].tag, ys[i].field, ys[i].key, ys[i].col = kind, tag, fld.encode(), key, col
+        keys = [np.ascontiguousarray(k, dtype=np.int64) for k in (spec.keys or [])]
+        ptr = [k.ctypes.data_as(P(c_i64)) for k in keys] + [None] * (3 - len(keys))
+        if spec.kind == FETCH_EDGE and spec.key_cols[2] < 0:
+            ptr[2] = None
+        plan = FetchPlanC(space, spec.kind, len(spec.tags), tags, spec.edge_type, (c_i32 * 3)(*spec.key_cols),
+                          len(keys[0]) if keys else 0, ptr[0], ptr[1], ptr[2], 1 if spec.distinct else 0,
+                          1 if spec.keep_missing else 0, len(spec.yields), ys)
+        return plan, (tags, ys, keys)
+
+    def _fetch_result(self, rc: int, out, rows: bool) -> GoResult:
+        err = self.L.ngx_last_error(self.h).decode() if rc else ""
+        if rc == E_DEVICE:
+            raise EngineError(rc, err)
+        o = out.contents
+        res = GoResult(ok=rc == 0, error=err, code=rc, col_types=o.col_types[:o.ncols] if o.ncols else [], rows=[],
+                       nrows=o.nrows, device_ms=o.device_ms, go_nrows=o.input_rows, tags_seen=o.tags_seen)
+        if rc == 0 and rows:
+            strings = ctypes.string_at(o.strings, o.strings_len) if o.strings_len else b""
+            res.rows = _cells(o.cells, o.nrows, o.ncols, strings)
+        return res
+
+    def fetch(self, space: int, spec: FetchSpec, result=None, rows: bool = True) -> GoResult:
+        """FETCH PROP ON over keys in HBM (ngx_fetch): the keys are the spec's host arrays, or with `result` (a
+        GoResultC of this engine's device-resident result, or an object with a .struct holding one) that result's
+        columns. GoResult.rows / nrows / col_types are the output's (the key columns, then the yields, in key
+        order), go_nrows the keys looked up, tags_seen the ON tags met, device_ms the call's. NGX_E_UNSUPPORTED
+        ("fetch: ...") and prepare-time errors come back as a result with the code and text."""
+        plan, _keep = self._fetch_plan(space, spec)
+        out = P(FetchResultC)()
+        r = None if result is None else ctypes.byref(getattr(result, "struct", result))
+        rc = self.L.ngx_fetch(self.h, r, ctypes.byref(plan), ctypes.byref(out))
+        try:
+            return self._fetch_result(rc, out, rows)
+        finally:
+            self.L.ngx_fetch_result_free(out)
+
+    def go_fetch(self, space: int, go: Union[str, ngql.GoSentence], spec: FetchSpec, pushdown: bool = True,
+                 now_sec: int = 0, compact: bool = True, rows: bool = True) -> GoResult:
+        """`GO ... | FETCH PROP ON ... $-.col ...` in one device call (ngx_go_fetch): the GO's rows stay in HBM and the
+        FETCH reads its key and input columns there; only the output rows cross. A refusal of the fetch stage
+        ("fetch: ...") comes back as a result with that code; the traversal's own refusal raises, as go() does."""
+        keep = self.prepare_go(space, go, pushdown=pushdown, now_sec=now_sec, on_device=True, yield_only=True, compact=compact)
+        plan, _keep = self._fetch_plan(space, spec)
+        out = P(FetchResultC)()
+        rc = self.L.ngx_go_fetch(self.h, ctypes.byref(keep.plan), ctypes.byref(plan), ctypes.byref(out))
+        try:
+            if rc in (E_DEVICE, E_UNSUPPORTED) and not self.L.ngx_last_error(self.h).decode().startswith("fetch:"):
+                raise EngineError(rc, self.L.ngx_last_error(self.h).decode())
+            return self._fetch_result(rc, out, rows)
+        finally:
+            self.L.ngx_fetch_result_free(out)
 
     def find_path(self, space: int, s: Union[str, ngql.FindPathSentence], from_vids: Optional[Sequence[int]] = None,
                   to_vids: Optional[Sequence[int]] = None, rows: bool = True) -> GoResult:

@@ -886,3 +886,138 @@ def parse_find_path(src: str) -> FindPathSentence:
         p.expect("kw", "STEPS")
     p.expect("eof")
     return s
+
+
+# ----------------------------------------------------------------------------- FETCH sentences
+# fetch_vertices_sentence / fetch_edges_sentence (parser.yy:861-944): FETCH PROP ON <labels> | * followed by a vid
+# list, `$-.col` / `$var.col`, edge keys `src -> dst[@rank]` or an edge key reference `$-.s -> $-.d[@$-.r]`, then an
+# optional yield_clause. FETCH, PROP and ON are matched as words (_word), so GO texts lex as before. Whether the
+# labels name tags or one edge type is decided by what follows them: an `->` makes it a FETCH on edges.
+@dataclass
+class FetchVerticesSentence:
+    tags: List[str] = field(default_factory=list)                 # ON order; ["*"]: every tag of the space
+    vids: List[Expr] = field(default_factory=list)                # constant vid expressions (from_type 0)
+    from_type: int = 0                                            # 0 literal vids, 1 $-.col, 2 $var.col (as GoSentence)
+    from_var: str = ""
+    from_col: str = ""
+    has_yield: bool = False
+    distinct: bool = False
+    yields: List[AggCol] = field(default_factory=list)
+
+
+@dataclass
+class FetchEdgesSentence:
+    edges: List[str] = field(default_factory=list)                # fetch_labels; the executor takes exactly one
+    keys: List[Tuple[Expr, Expr, int]] = field(default_factory=list)   # (src expr, dst expr, rank) (from_type 0)
+    from_type: int = 0
+    src_ref: Optional[Prop] = None                                # edge_key_ref: $-.s -> $-.d [@ $-.r], or $var's
+    dst_ref: Optional[Prop] = None
+    rank_ref: Optional[Prop] = None
+    has_yield: bool = False
+    distinct: bool = False
+    yields: List[AggCol] = field(default_factory=list)
+
+    def ref_string(self) -> str:                                  # EdgeKeyRef::toString
+        out = self.src_ref.to_string() + "->" + self.dst_ref.to_string()
+        return out + ("@" + self.rank_ref.to_string() if self.rank_ref is not None else "")
+
+
+def is_fetch(src: str) -> bool:
+    return re.match(r"\s*FETCH\b", src, re.I) is not None
+
+
+def _fetch_vid(p: Parser) -> Expr:
+    """vid (parser.yy:646-656): unary_integer | function_call_expression | uuid_expression."""
+    t = p.peek()
+    if t.kind in ("ref", "var"):
+        raise SyntaxError(f"syntax error near `{t.text}'")
+    e = p.primary() if p.is_op("-") or p.is_op("+") else p.base()
+    if isinstance(e, Unary) and e.op == UNARY_OPS["+"] and isinstance(e.operand, Prim):
+        e = e.operand
+    if isinstance(e, Prim) and isinstance(e.value, int) and not isinstance(e.value, bool):
+        return e
+    if isinstance(e, Func):
+        return e
+    raise SyntaxError(f"syntax error near `{t.text}'")
+
+
+def _fetch_ref(p: Parser) -> Prop:
+    """input_ref_expression | var_ref_expression"""
+    t = p.peek()
+    if not (t.kind == "ref" and t.text == "$-" or t.kind == "var"):
+        raise SyntaxError(f"syntax error near `{t.text}'")
+    return p.base()
+
+
+def parse_fetch(src: str):
+    p = Parser(src)
+    for word in ("FETCH", "PROP", "ON"):
+        if _word(p, word) is None:
+            raise SyntaxError(f"expected {word}, got {p.peek().text!r}")
+    labels = []
+    if p.accept("op", "*"):
+        labels = ["*"]
+    else:
+        while True:
+            labels.append(p.label())
+            # `ON a, b 1, 2`: a comma continues the labels only while a label follows it
+            if p.is_op(",") and p.peek(1).kind in ("name", "kw") and not (p.peek(2).kind == "op" and p.peek(2).text == "("):
+                p.take()
+                continue
+            break
+    t = p.peek()
+    s = None
+    if t.kind == "ref" and t.text == "$-" or t.kind == "var":
+        first = _fetch_ref(p)
+        if p.accept("op", "->"):
+            if labels == ["*"]:
+                raise SyntaxError("syntax error near `->'")
+            s = FetchEdgesSentence(edges=labels, from_type=1 if first.kind == K_INPUT_PROP else 2, src_ref=first)
+            s.dst_ref = _fetch_ref(p)
+            if p.accept("op", "@"):
+                s.rank_ref = _fetch_ref(p)
+            for r in (s.dst_ref, s.rank_ref):                     # the grammar has no mixed $- / $var key
+                if r is not None and r.kind != first.kind:
+                    raise SyntaxError("syntax error near `%s'" % r.to_string())
+        else:
+            s = FetchVerticesSentence(tags=labels, from_type=1 if first.kind == K_INPUT_PROP else 2,
+                                      from_var=first.alias if first.kind == K_VAR_PROP else "", from_col=first.prop)
+    else:
+        first = _fetch_vid(p)
+        if p.is_op("->"):
+            if labels == ["*"]:
+                raise SyntaxError("syntax error near `->'")
+            s = FetchEdgesSentence(edges=labels)
+            e = first
+            while True:
+                p.expect("op", "->")
+                d = _fetch_vid(p)
+                rank = 0
+                if p.accept("op", "@"):
+                    neg = False
+                    if p.accept("op", "-"):
+                        neg = True
+                    else:
+                        p.accept("op", "+")
+                    tk = p.peek()
+                    if tk.kind not in ("int", "hex"):
+                        raise SyntaxError(f"expected an integer, got {tk.text!r}")
+                    p.take()
+                    rank = -int(tk.text, 0) if neg else int(tk.text, 0)
+                s.keys.append((e, d, rank))
+                if not p.accept("op", ","):
+                    break
+                e = _fetch_vid(p)
+        else:
+            s = FetchVerticesSentence(tags=labels, vids=[first])
+            while p.accept("op", ","):
+                s.vids.append(_fetch_vid(p))
+    if p.accept("kw", "YIELD"):
+        s.has_yield = True
+        if p.accept("kw", "DISTINCT"):
+            s.distinct = True
+        s.yields = _agg_columns(p)
+        if not s.yields:
+            raise SyntaxError("syntax error near `YIELD'")
+    p.expect("eof")
+    return s

@@ -25,6 +25,11 @@ library, include/nebula_gn.h ngx_go with input_* set):
     [UPTO n STEPS]` (nebula_amd/findpath.py), when the caller opts in with find_path=True; FIND SHORTEST PATH runs
     in one device call where the backend has it (ngx_find_path; Pipeline._find_path). It hands no result on: a
     sentence piped behind it runs without input.
+  - FetchVerticesExecutor / FetchEdgesExecutor (src/graph/FetchVerticesExecutor.cpp, FetchEdgesExecutor.cpp): `FETCH
+    PROP ON <tags> | * <vids> | $-.col | $var.col` and `FETCH PROP ON <edge> <src> -> <dst>[@rank] | $-.s -> $-.d`
+    (nebula_amd/fetch.py), when the caller opts in with fetch=True and hands the space's schemas (catalog=). It
+    calls onResult_: its rows feed the sentence piped behind it. The key lookup and the property gather run in one
+    device call where the backend has it (ngx_fetch; behind a plain head GO, ngx_go_fetch; Pipeline._fetch).
 GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
 default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
@@ -34,6 +39,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
+from . import fetch as fetchmod
 from . import findpath, groupby, ngql, orderby, setop
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
@@ -111,6 +117,18 @@ def _unwrap(text: str) -> str:
     return t
 
 
+def plain_go(s: ngql.GoSentence) -> bool:
+    """A GO a device-resident call can take as its head: literal vids, no DISTINCT, a YIELD without aggregates and
+    without `$-` / `$var` props."""
+    if s.from_type or s.distinct or not s.yields:
+        return False
+    for y in s.yields:
+        if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
+                any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
+            return False
+    return True
+
+
 def expand_input_star(s: ngql.GoSentence, names: Optional[Sequence[str]], var: str = "") -> None:
     """YieldClauseWrapper::needAllPropsFromInput / needAllPropsFromVar: `$-.*` / `$v.*` -> one
     column per input column."""
@@ -143,8 +161,14 @@ class Pipeline:
     def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
                  order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
                  set_ops: bool = False, device_set_op: bool = True, find_path: bool = False,
-                 device_find_path: bool = True, **go_kw):
-        """find_path=True: FIND PATH sentences run (off by default, as order_limit and set_ops are);
+                 device_find_path: bool = True, fetch: bool = False, device_fetch: bool = True, catalog=None, **go_kw):
+        """fetch=True: FETCH PROP ON sentences run (off by default, as the other opt-ins are); catalog is the
+        space's fetch.Catalog (partition count, tag and edge schemas: what the executors ask the schema manager);
+        an Engine backend hands its own (Engine.catalog), the oracle backend needs it passed.
+        device_fetch=False: every FETCH takes the host restatement (fetch.py) even where the backend could look the
+        keys up in HBM. fetch_fallbacks counts the device calls refused with "fetch: ...", fetch_refusal keeps the
+        last refusal's text.
+        find_path=True: FIND PATH sentences run (off by default, as order_limit and set_ops are);
         device_find_path=False: every FIND PATH sentence takes the host restatement (findpath.py) even where the
         backend could search in HBM. find_path_fallbacks counts the device calls refused with "find path: ...".
         set_ops=True: UNION / INTERSECT / MINUS sentences run (off by default, as order_limit is: they are
@@ -164,6 +188,15 @@ class Pipeline:
         self.device_find_path = device_find_path
         self.find_path_fallbacks = 0
         self.find_path_refusal = ""                               # the last refusal's text
+        self.fetch = fetch
+        self.device_fetch = device_fetch
+        if catalog is None and fetch and hasattr(backend, "catalog"):
+            catalog = backend.catalog(space)                      # an Engine knows the schemas it was given
+        if fetch and catalog is None:
+            raise PipelineError("fetch=True needs the space's schemas: catalog=fetch.Catalog(...)")
+        self.catalog = catalog
+        self.fetch_fallbacks = 0
+        self.fetch_refusal = ""
         self.device_group_by = device_group_by
         self.order_limit = order_limit
         self.device_order_by = device_order_by
@@ -245,12 +278,8 @@ class Pipeline:
             s, g = ngql.parse_go(go_text), ngql.parse_group_by(gb_text)
             aliases = groupby.prepare(g)
             names = s.column_names(self.edge_names)
-            if s.from_type or s.distinct or not s.yields or len(set(names)) != len(names):
+            if not plain_go(s) or len(set(names)) != len(names):
                 return None
-            for y in s.yields:
-                if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
-                        any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
-                    return None
             groups = groupby.check_all(g, aliases, names)
             if len(groups) > 4 or not all(groupby._is_input(c.expr) for c in groups):
                 return None
@@ -313,12 +342,8 @@ class Pipeline:
         try:
             s, lim = ngql.parse_go(go_text), ngql.parse_limit(lim_text)
             names = s.column_names(self.edge_names)
-            if s.from_type or s.distinct or not s.yields or len(set(names)) != len(names):
+            if not plain_go(s) or len(set(names)) != len(names):
                 return None
-            for y in s.yields:
-                if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
-                        any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
-                    return None
             factors = []
             if ob_text is not None:
                 for col, desc in ngql.parse_order_by(ob_text).factors:
@@ -437,12 +462,8 @@ class Pipeline:
                 if len(_split(text, "|")) > 1 or not text.strip().upper().startswith("GO"):
                     return None
                 s = ngql.parse_go(text)
-                if s.from_type or s.distinct or not s.yields:
+                if not plain_go(s):
                     return None
-                for y in s.yields:
-                    if (isinstance(y.expr, ngql.Func) and y.expr.name.upper() in ngql.AGG_FUNCS) or \
-                            any(k in (ngql.K_INPUT_PROP, ngql.K_VAR_PROP) for k, _, _ in y.expr.props()):
-                        return None
                 pair.append(s)
             if len(pair[0].yields) != len(pair[1].yields):
                 return None
@@ -526,6 +547,77 @@ class Pipeline:
             return Outcome(False, str(e), ["_path_"])
         return Outcome(True, "", names, types, rows)
 
+    def _fetch(self, text: str, inp: Optional[Interim], go_text: Optional[str] = None) -> Optional[Outcome]:
+        """A FETCH sentence: on the device where the backend has it and takes the sentence, else the executors
+        restated on the host (fetch.run). go_text: the plain head GO in front of it, to run in the same device call
+        (ngx_go_fetch); None is returned when that call cannot be made and the two sentences run one by one."""
+        try:
+            s = ngql.parse_fetch(text)
+        except (SyntaxError, ValueError) as e:
+            return None if go_text is not None else Outcome(False, "SyntaxError: %s" % e)
+        vertices = isinstance(s, ngql.FetchVerticesSentence)
+        first = ["VertexID"] if vertices else [s.edges[0] + k for k in ("._src", "._dst", "._rank")] if s.edges else []
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            if self.device_fetch and getattr(self.backend, "device_fetch", False):
+                r = self._device_fetch(s, inp, go_text, kw)
+                if r is not None:
+                    return r
+            if go_text is not None:
+                return None
+            names, types, rows = fetchmod.run(self.backend, self.space, self.catalog, s, inp, self.variables,
+                                              now_sec=kw.get("now_sec", 0))
+        except fetchmod.FetchError as e:
+            if go_text is not None:
+                return None
+            return Outcome(False, str(e), first)
+        return Outcome(True, "", names, types, rows)
+
+    def _device_fetch(self, s, inp: Optional[Interim], go_text: Optional[str], kw) -> Optional[Outcome]:
+        """The sentence through Engine.fetch / Engine.go_fetch; None: the host restatement has to run (a "fetch: ..."
+        refusal is counted), or, with go_text, the sentences run one by one. The prepare stage is the host's
+        (fetch.prepare_vertices / prepare_edges), so every Status text is the one the host path gives."""
+        g = None
+        if go_text is not None:
+            g = self._plain_go(go_text)
+            if g is None or not s.from_type or s.from_type != 1:
+                return None
+            names = g.column_names(self.edge_names)
+            if len(set(names)) != len(names):
+                return None
+            # the prepare stage wants the input's names and (for `$-.x` in YIELD) types; the rows stay in HBM
+            inp = Interim(names, [], [tuple(("int", 0) for _ in names)])
+        spec = fetchmod.device_spec(self.catalog, s, inp, self.variables, placeholder=g is not None)
+        if spec is None:                                          # empty inputs, or a shape only the host words
+            return None
+        if g is not None:
+            try:
+                r = self.backend.go_fetch(self.space, g, spec, **kw)
+            except RuntimeError as e:
+                if getattr(e, "code", 0) == -1002:                # the device-resident GO itself: the plain path decides
+                    return None
+                raise
+        else:
+            r = self.backend.fetch(self.space, spec)
+        if not r.ok:
+            if r.code == -1002 and r.error.startswith("fetch:"):
+                self.fetch_fallbacks += 1
+                self.fetch_refusal = r.error
+                return None
+            if g is not None:                                     # the GO's own error: the plain path words it
+                return None
+            return Outcome(False, r.error, spec.names)
+        names, types, rows = fetchmod.device_rows(spec, r)
+        return Outcome(True, "", names, types, rows)
+
+    def _plain_go(self, go_text: str):
+        """The GoSentence of a plain GO (plain_go, the condition _device_spec sets too), else None."""
+        try:
+            s = ngql.parse_go(go_text)
+        except (SyntaxError, ValueError):
+            return None
+        return s if plain_go(s) else None
+
     def _operand(self, text: str) -> Outcome:
         """One operand of a set sentence: a piped sentence, or a parenthesised set sentence."""
         body = _unwrap(text)
@@ -549,6 +641,14 @@ class Pipeline:
                         ngql.parse_limit(body)
                 except (SyntaxError, ValueError) as e:
                     return Outcome(False, "SyntaxError: %s" % e)
+        if self.fetch:
+            for part in parts:
+                body = _unwrap(part)
+                if len(_split(body, "|")) == 1 and ngql.is_fetch(body):
+                    try:
+                        ngql.parse_fetch(body)
+                    except (SyntaxError, ValueError) as e:
+                        return Outcome(False, "SyntaxError: %s" % e)
         cur = inp
         out = None
         skip = 0
@@ -560,6 +660,14 @@ class Pipeline:
                     cur = Interim.from_result(out.names, out.col_types, out.rows)
                 continue
             host_group = False
+            if self.fetch and self.device_fetch and getattr(self.backend, "device_fetch", False) and i + 1 < len(parts) \
+                    and cur is None and body.upper().startswith("GO") and ngql.is_fetch(_unwrap(parts[i + 1])):
+                dev = self._fetch(_unwrap(parts[i + 1]), None, go_text=body)
+                if dev is not None:
+                    out, skip = dev, 1
+                    if not out.ok:
+                        return out
+                    continue
             if self.order_limit and self.device_order_by and self.device_group_by and self.device_group_order \
                     and getattr(self.backend, "device_group_order", False) and i + 2 < len(parts) \
                     and body.upper().startswith("GO") and ngql.is_group_by(_unwrap(parts[i + 1])):
@@ -609,6 +717,8 @@ class Pipeline:
                 out = self._order_by(body, cur)
             elif self.order_limit and ngql.is_limit(body):
                 out = self._limit(body, cur)
+            elif self.fetch and ngql.is_fetch(body):
+                out = self._fetch(body, cur)
             elif self.find_path and ngql.is_find_path(body):
                 out = self._find_path(body, cur)
                 if not out.ok:
@@ -647,7 +757,8 @@ class Pipeline:
 def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
         order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
         set_ops: bool = False, device_set_op: bool = True, find_path: bool = False, device_find_path: bool = True,
-        **go_kw) -> Outcome:
+        fetch: bool = False, device_fetch: bool = True, catalog=None, **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
                     device_order_by=device_order_by, device_group_order=device_group_order, set_ops=set_ops,
-                    device_set_op=device_set_op, find_path=find_path, device_find_path=device_find_path, **go_kw).run(text)
+                    device_set_op=device_set_op, find_path=find_path, device_find_path=device_find_path, fetch=fetch,
+                    device_fetch=device_fetch, catalog=catalog, **go_kw).run(text)
