@@ -4086,6 +4086,10 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                     R.hopFrontier.back() = fF;
                     R.hopEdges.back() = fE;
                     if (!R.hopNext.empty()) R.hopNext.back() = fF;
+                    if (fF == 0) {                              // GO_EXIT: the hop before left no frontier, so this
+                        R.hopFrontier.pop_back();               // step was never taken (as the host-sized and the
+                        R.hopEdges.pop_back();                  // dyn paths report it): no statistics for it
+                    }
                     c->addBytes("final", fE * (keyReadBytes + kfBytes));
                     c->addBytes("compact_degrees", fF * 8 + fF * static_cast<uint64_t>(hs.n) * 24);
                 }

@@ -1,0 +1,848 @@
+"""A model of GO that shares nothing with the code under test, the shaped graphs it is run on, and the loaders the
+tests put those graphs into an Engine and into the oracle with.
+
+The model is plain Python over an edge list `(src vid, dst vid, type, rank, (p0, p1, b))` plus optional tag rows
+`{vid: x}`. It restates GoExecutor's rules (src/graph/GoExecutor.cpp of the reference):
+  * an edge `a -> b` of type t and rank r is stored twice: the out row `(a, +t, r, b)` and the in row `(b, -t, r, a)`,
+    both with the edge's properties. FORWARD a hop scans the `+t` rows of its frontier for every OVER type t,
+    REVERSELY the `-t` rows, BIDIRECT both (stepOut, getStepOutProps);
+  * the seeds are the FROM list as written: a vid listed twice is scanned twice, a vid without rows scans nothing; only
+    YIELD DISTINCT makes the list a set (execute, :123-129);
+  * a hop's next frontier is the set of the `dst` fields of the rows it scanned, whatever WHERE says
+    (getDstIdsFromRespWithBackTrack); an empty next frontier ends the query (no further hop is counted);
+  * `GO M TO N STEPS` records hops M .. N (plain `N STEPS`: hop N only); WHERE and YIELD are evaluated for the rows
+    of the record hops only (processFinalResult);
+  * for a scanned row `(v, s, r, w)`: `_src` is v, `_dst` is w, `_rank` is r, `_type` is the stored signed type s
+    (so REVERSELY `_src` is the edge's destination and `_type` is negative);
+  * with more than one OVER type, `x._dst` of a row of another type is 0, and every other `x.prop` of it is the
+    column type's default, 0 for integers (getEdgeDstId, getAliasProp);
+  * a pushed-down WHERE: FORWARD, on the last hop, storage evaluates the WHERE first, and there an alias of another
+    type than the row's is an error that drops the row (QueryBaseProcessor.inl:539-601 of the reference: "Ignore this
+    edge"), so with several OVER types only the rows of the type the WHERE names survive; REVERSELY, BIDIRECT, on earlier
+    record hops and with pushdown off graphd alone evaluates it, with the defaults above;
+  * `$^.t.x` / `$$.t.x` of a vertex without the tag is the default, 0, where graphd evaluates them (getSrcTagProp,
+    getDstTagProp). That is the whole rule only for the one form here that reads tags: its YIELD reads no edge property
+    but `_dst`, so the storage request is structure-only and storage never evaluates the pushed WHERE
+    (QueryBaseProcessor.inl:520). With an edge property in the YIELD, a pushed WHERE that reads `$^.t.x` fails in
+    storage for a source without the tag row ("Invalid Tag Filter", .inl:582-596) and drops the edge: the model does
+    NOT restate that, so a new form of that kind needs the rule added first (the host test would show the difference).
+The model parses and evaluates no nGQL: each query form of FORMS pairs the text with Python callables.
+
+Cells are `(kind, value)` as the engine and the oracle hand them out: "id" for `_src` / `_dst`, "int" for `_rank`,
+`_type` and INT properties.
+"""
+import random
+from collections import namedtuple
+
+import numpy as np
+
+from nebula_amd import kvfmt
+from tests import fixtures
+
+# ----------------------------------------------------------------------------- constants of the kernels under test
+# Mirrored from nebula_amd/csrc (tests/test_goref_host.py asserts each against the header it is named in, so a change
+# of a constant moves the tests).
+K_SEED_FUSE_MAX = 4096          # kernels.h   kSeedFuseMax
+K_CHUNK = 2048                  # kargs.h     kChunk
+K_WG = 256                      # final_kernels.h WG
+K_SPARSE_SUB = K_CHUNK // K_WG  # kernels.hip kSparseSub = CE / WG (CE = kChunk): 8 slices of 256 edges
+K_PULL_K = 16                   # kernels.h   kPullK
+K_PULL_WINDOW = 2048            # kernels.h   kPullWindow
+K_PULL_SEG = 1024               # kernels.h   kPullSeg
+K_PULL_MAX_SLOTS = 4            # kernels.h   kPullMaxSlots
+K_COMPACT_TILE = 4096           # kernels.h   kCompactTile
+K_RESV_SHIFT = 16               # kargs.h     kResvShift
+K_RESV_GROUPS = 8               # kargs.h     kResvGroups
+CONSTANTS = {
+    "kernels.h": {"kSeedFuseMax": K_SEED_FUSE_MAX, "kPullK": K_PULL_K, "kPullWindow": K_PULL_WINDOW,
+                  "kPullSeg": K_PULL_SEG, "kPullMaxSlots": K_PULL_MAX_SLOTS, "kCompactTile": K_COMPACT_TILE},
+    "kargs.h": {"kChunk": K_CHUNK, "kResvShift": K_RESV_SHIFT, "kResvGroups": K_RESV_GROUPS},
+    "final_kernels.h": {"WG": K_WG},
+}
+
+TYPE_OF = {"e": 1, "f": 2, "g": 3, "h": 4, "i": 5}
+NAME_OF = {t: n for n, t in TYPE_OF.items()}
+EDGE_FIELDS = [("p0", kvfmt.INT), ("p1", kvfmt.INT), ("b", kvfmt.INT)]
+TAG_ID = 11
+SCHEMA = [fixtures.SchemaDef(True, t, n, EDGE_FIELDS) for n, t in TYPE_OF.items()] + \
+         [fixtures.SchemaDef(False, TAG_ID, "t", [("x", kvfmt.INT)])]
+FORWARD, REVERSELY, BIDIRECT = 0, 1, 2
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def default_props(a, b, t, r):
+    """(p0 in 0 .. 99, p1 over the 62-bit range, b in -100 .. 99) from a hash of the edge's key."""
+    h = (a * 2654435761 + b * 40503 + t * 97 + r * 31 + 17) & 0xFFFFFFFFFFFF
+    return (h % 100, (h * 6364136223846793005 + 1442695040888963407) % (1 << 62) - (1 << 61), (h >> 9) % 200 - 100)
+
+
+def edge(a, b, t=1, r=0, props=None):
+    return (a, b, t, r, tuple(props) if props is not None else default_props(a, b, t, r))
+
+
+class Graph:
+    """vids: the vertex table (every endpoint of an edge is in it); edges: `edge()` tuples, no (src, dst, type, rank)
+    twice; types: the edge types that get a slot pair (default: those with an edge); tags: {vid: x} or None."""
+
+    def __init__(self, vids, edges, types=None, tags=None):
+        self.vids = sorted(set(vids))
+        self.edges = list(edges)
+        self.types = sorted(types if types is not None else {x[2] for x in self.edges})
+        self.tags = tags
+        have = set(self.vids)
+        keys = set()
+        for a, b, t, r, _ in self.edges:
+            assert a in have and b in have and t in self.types, (a, b, t)
+            assert (a, b, t, r) not in keys, ("an edge twice", a, b, t, r)
+            keys.add((a, b, t, r))
+        self._rows = None
+
+    def rows(self):
+        """{(vertex, signed type): [(rank, other end, props)]}: the stored rows."""
+        if self._rows is None:
+            rows = {}
+            for a, b, t, r, p in self.edges:
+                rows.setdefault((a, t), []).append((r, b, p))
+                rows.setdefault((b, -t), []).append((r, a, p))
+            self._rows = rows
+        return self._rows
+
+    def out_degree(self, v, types):
+        return sum(len(self.rows().get((v, t), ())) for t in types)
+
+
+# ----------------------------------------------------------------------------- the model
+Row = namedtuple("Row", "src dst st rank props g")           # one scanned row, st its stored signed type
+Model = namedtuple("Model", "rows hop_edges hop_frontier")
+
+
+def go(graph, seeds, over, direction, m, n, where, yields, distinct=False, pushed_type=None):
+    """GO m TO n STEPS FROM seeds OVER over (type ids) in `direction`; where: Row -> bool or None; yields: one
+    callable Row -> cell per column; pushed_type: the type of the alias a pushed-down WHERE reads (None: not pushed). Returns Model(rows as a list of cell tuples, hop_edges, hop_frontier)."""
+    stored = graph.rows()
+    scan = {FORWARD: list(over), REVERSELY: [-t for t in over], BIDIRECT: list(over) + [-t for t in over]}[direction]
+    frontier = list(seeds)
+    if distinct:
+        frontier = list(dict.fromkeys(frontier))
+    out, hop_edges, hop_frontier, seen = [], [], [], set()
+    for hop in range(1, n + 1):
+        hop_frontier.append(len(frontier))
+        scanned = [Row(v, w, st, r, p, graph) for v in frontier for st in scan for r, w, p in stored.get((v, st), ())]
+        hop_edges.append(len(scanned))
+        if hop >= m:
+            for row in scanned:
+                if pushed_type is not None and direction == FORWARD and hop == n and abs(row.st) != pushed_type:
+                    continue
+                if where is not None and not where(row):
+                    continue
+                cells = tuple(y(row) for y in yields)
+                if distinct:
+                    if cells in seen:
+                        continue
+                    seen.add(cells)
+                out.append(cells)
+        frontier = list({row.dst for row in scanned})
+        if not frontier:
+            break
+    return Model(out, hop_edges, hop_frontier)
+
+
+def _of(row, t, name):
+    """`alias.name` where the alias is edge type t."""
+    if abs(row.st) != t:
+        return 0
+    if name == "_src":
+        return row.src
+    if name == "_dst":
+        return row.dst
+    if name == "_rank":
+        return row.rank
+    if name == "_type":
+        return row.st
+    return row.props[("p0", "p1", "b").index(name)]
+
+
+def _cmod(a, b):
+    """C++ `%`: the quotient truncates towards zero."""
+    q = abs(a) // abs(b)
+    if (a < 0) != (b < 0):
+        q = -q
+    return a - q * b
+
+
+def _tag(row, vid):
+    return (row.g.tags or {}).get(vid, 0)
+
+
+def _col(kind, name, k=0):
+    return lambda over: (lambda row: (kind, _of(row, over[k], name)))
+
+
+# A form: the text after `OVER ... [direction]` with {a} / {b} for the first / second OVER alias, the predicate and the
+# YIELD columns as functions of the OVER type ids, DISTINCT, and how many OVER types it needs at least.
+# where_alias: the OVER alias an edge-reading WHERE names (what a pushed-down filter keeps), None if it reads no edge.
+Form = namedtuple("Form", "name tail where yields distinct min_over tags where_alias")
+FORMS = {f.name: f for f in [
+    Form("bench", "WHERE {a}.p0 < 50 YIELD {a}._dst, {a}._rank, {a}.p0, {a}.p1",
+         lambda over: (lambda row: _of(row, over[0], "p0") < 50),
+         [_col("id", "_dst"), _col("int", "_rank"), _col("int", "p0"), _col("int", "p1")], False, 1, False, 0),
+    Form("all", "YIELD {a}._dst, {a}.p1", None, [_col("id", "_dst"), _col("int", "p1")], False, 1, False, None),
+    Form("keys", "YIELD {a}._src, {a}._dst, {a}._type, {a}._rank", None,
+         [_col("id", "_src"), _col("id", "_dst"), _col("int", "_type"), _col("int", "_rank")], False, 1, False, None),
+    Form("mod", "WHERE {a}.p1 % 7 == 1 YIELD {a}._dst, {a}.p1",
+         lambda over: (lambda row: _cmod(_of(row, over[0], "p1"), 7) == 1),
+         [_col("id", "_dst"), _col("int", "p1")], False, 1, False, 0),
+    Form("signed", "WHERE {a}.b < 0 YIELD {a}._dst, {a}.b",
+         lambda over: (lambda row: _of(row, over[0], "b") < 0),
+         [_col("id", "_dst"), _col("int", "b")], False, 1, False, 0),
+    Form("distinct", "YIELD DISTINCT {a}._dst", None, [_col("id", "_dst")], True, 1, False, None),
+    Form("tags", "WHERE $^.t.x >= 0 YIELD {a}._dst, $^.t.x, $$.t.x",
+         lambda over: (lambda row: _tag(row, row.src) >= 0),
+         [_col("id", "_dst"), lambda over: (lambda row: ("int", _tag(row, row.src))),
+          lambda over: (lambda row: ("int", _tag(row, row.dst)))], False, 1, True, None),
+    Form("multi", "WHERE {a}.b < 50 YIELD {a}._dst, {b}._dst, {a}._rank, {b}._rank, {a}.b, {b}.b",
+         lambda over: (lambda row: _of(row, over[0], "b") < 50),
+         [_col("id", "_dst"), _col("id", "_dst", 1), _col("int", "_rank"), _col("int", "_rank", 1), _col("int", "b"),
+          _col("int", "b", 1)], False, 2, False, 0),
+    Form("multi_all", "YIELD {a}._dst, {b}._dst, {a}._rank, {b}._rank, {a}.b, {b}.b", None,
+         [_col("id", "_dst"), _col("id", "_dst", 1), _col("int", "_rank"), _col("int", "_rank", 1), _col("int", "b"),
+          _col("int", "b", 1)], False, 2, False, None),
+]}
+_DIR = {FORWARD: "", REVERSELY: " REVERSELY", BIDIRECT: " BIDIRECT"}
+KIND_TYPE = {"id": kvfmt.VID, "int": kvfmt.INT}
+
+
+def sentence(form, seeds, over, direction=FORWARD, m=None, n=1):
+    """The nGQL text of a form; over: edge names."""
+    f = FORMS[form]
+    assert len(over) >= f.min_over
+    steps = "%d STEPS" % n if m is None else "%d TO %d STEPS" % (m, n)
+    tail = f.tail.replace("{a}", over[0]).replace("{b}", over[1] if len(over) > 1 else over[0])
+    return "GO %s FROM %s OVER %s%s %s" % (steps, ", ".join(str(int(v)) for v in seeds), ", ".join(over), _DIR[direction], tail)
+
+
+def model(graph, form, seeds, over, direction=FORWARD, m=None, n=1, pushdown=True):
+    f = FORMS[form]
+    types = [TYPE_OF[x] for x in over]
+    return go(graph, seeds, types, direction, n if m is None else m, n, f.where(types) if f.where else None,
+              [y(types) for y in f.yields], f.distinct,
+              types[f.where_alias] if pushdown and f.where_alias is not None else None)
+
+
+def column_kinds(form):
+    return [y([1, 2])(Row(0, 0, 1, 0, (0, 0, 0), Graph([0], [])))[0] for y in FORMS[form].yields]
+
+
+# ----------------------------------------------------------------------------- the comparator
+def typed_rows(rows):
+    return sorted(tuple((k, int(v)) for k, v in r) for r in rows)
+
+
+def assert_same(got, want, what=""):
+    """got: an engine or oracle GoResult (or a Model); want: the Model. Sorted typed rows, the edges scanned per hop
+    and the frontier per hop, all exact."""
+    assert getattr(got, "ok", True), (what, getattr(got, "error", ""))
+    edges = got.hop_edges if hasattr(got, "hop_edges") else got.hop_scanned
+    assert [int(x) for x in edges] == list(want.hop_edges), (what, "hop_edges", list(edges), want.hop_edges)
+    assert [int(x) for x in got.hop_frontier] == list(want.hop_frontier), (what, "hop_frontier", list(got.hop_frontier),
+                                                                           want.hop_frontier)
+    a, b = typed_rows(got.rows), typed_rows(want.rows)
+    if a != b:
+        sa, sb = set(a), set(b)
+        raise AssertionError((what, "rows", len(a), len(b), sorted(sa - sb)[:3], sorted(sb - sa)[:3]))
+
+
+def columns(want, ncol):
+    """The model's rows as int64 columns (for oracle.row_digest and for compact device results)."""
+    return [np.array([r[c][1] for r in want.rows], dtype=np.int64) for c in range(ncol)]
+
+
+# ----------------------------------------------------------------------------- loaders
+def _key(x):
+    return (x & (1 << 64) - 1).to_bytes(8, "little")
+
+
+_space = [300]
+
+
+def new_space():
+    _space[0] += 1
+    return _space[0]
+
+
+def csr_slots(graph):
+    """ngx_load_csr's arrays of a Graph: (vpart, vid, slots), a slot pair (+t, -t) per type of graph.types, the rows'
+    edges in key order (rank, then dst, by their little-endian bytes)."""
+    row = {v: i for i, v in enumerate(graph.vids)}
+    nv = len(graph.vids)
+    slots = []
+    for t in graph.types:
+        for sign in (1, -1):
+            lists = [[] for _ in range(nv)]
+            for a, b, tt, r, p in graph.edges:
+                if tt == t:
+                    lists[row[a] if sign > 0 else row[b]].append((r, b if sign > 0 else a, p))
+            off, dst, rank, cols = [0], [], [], ([], [], [])
+            for lst in lists:
+                for r, d, p in sorted(lst, key=lambda x: (_key(x[0]), _key(x[1]))):
+                    dst.append(d)
+                    rank.append(r)
+                    for k in range(3):
+                        cols[k].append(p[k])
+                off.append(len(dst))
+            slots.append((sign * t, np.array(off, np.uint64), np.array(dst, np.int64), [np.array(c, np.int64) for c in cols],
+                          np.array(rank, np.int64)))
+    return np.ones(nv, np.int32), np.array(graph.vids, np.int64), slots
+
+
+def load_engine_csr(e, graph, space=None, arrays=None):
+    """The graph through ngx_load_csr (exact layout, exact mirrors, one part, no tag rows). Returns the space."""
+    space = space or new_space()
+    e.add_space(space, 1)
+    for s in SCHEMA:
+        e.add_schema(space, s.is_edge, s.sid, s.name, s.fields)
+    e.load_csr(space, *(arrays or csr_slots(graph)))
+    e.commit(space)
+    return space
+
+
+def kv_batch(graph):
+    b = kvfmt.KVBatch()
+    types = [t for _, t in EDGE_FIELDS]
+    for a, d, t, r, p in graph.edges:
+        row = kvfmt.encode_row(types, list(p))
+        b.put(kvfmt.edge_key(1, a, t, r, d), row)
+        b.put(kvfmt.edge_key(1, d, -t, r, a), row)
+    for v, x in sorted((graph.tags or {}).items()):
+        b.put(kvfmt.vertex_key(1, v, TAG_ID), kvfmt.encode_row([kvfmt.INT], [x]))
+    return b
+
+
+def dataset(graph, space=None):
+    return fixtures.Dataset(space or new_space(), 1, SCHEMA, kv_batch(graph))
+
+
+def load_engine_kv(e, graph, space=None):
+    """The graph as KV rows (out and in row per edge, a tag row per entry of graph.tags). Returns the space."""
+    ds = dataset(graph, space)
+    ds.load_engine(e)
+    return ds.space
+
+
+def load_oracle(o, graph, space=None):
+    ds = dataset(graph, space)
+    ds.load_oracle(o)
+    return ds.space
+
+
+# ----------------------------------------------------------------------------- shaped graphs
+# Every generator returns (Graph, seeds). Unless said otherwise row r of the vertex table is vid r + 1 and the
+# traversal is `GO 2 STEPS`: the seeds' out-edges (hop 1) select the frontier the hop under test expands.
+def fan(frontier_rows, adj, nv, types=None, tags=None, extra=()):
+    """Vertex nv + 1 (the seed, the last row) points over type 1 at `frontier_rows`; adj: {row: [(dst row, type, rank)
+    or dst row]} the edges of the hop under test."""
+    edges = [edge(nv + 1, r + 1, 1, 0) for r in sorted(set(frontier_rows))]
+    for r, lst in adj.items():
+        for x in lst:
+            d, t, rk = x if isinstance(x, tuple) else (x, 1, 0)
+            edges.append(edge(r + 1, d + 1, t, rk))
+    edges += list(extra)
+    return Graph(range(1, nv + 2), edges, types=types, tags=tags), [nv + 1]
+
+
+def frontier_edges(n, seed=0):
+    """A hop-2 frontier with exactly n edges: degrees drawn from {0, 1, 2, 3, 7, 19, 64, 300} until n are placed,
+    the destinations spread over the rows; every row with edges is in the frontier, as are some without."""
+    rnd = random.Random(1000 + n + seed)
+    nv = max(n // 3, 8) + 40
+    adj, left, r = {}, n, 0
+    while left:
+        d = min(left, rnd.choice([0, 0, 1, 2, 3, 7, 19, 64, 300]), nv)
+        if d:
+            adj[r] = rnd.sample(range(nv), d)
+        left -= d
+        r += 1
+        assert r < nv
+    g, seeds = fan(list(range(r)) + [nv - 1], adj, nv)
+    assert sum(len(a) for a in adj.values()) == n
+    return g, seeds
+
+
+def supernode_midchunk():
+    """Rows 0 .. 9 of degree 1, row 10 of degree 5000 (frontier positions 10 .. 5009: it starts mid-chunk and covers
+    chunks 0, 1 and 2), rows 11 .. 20 of degree 1; all of them in the frontier."""
+    nv = 5200
+    adj = {r: [(r * 37) % 5000 + 21] for r in list(range(10)) + list(range(11, 21))}
+    adj[10] = list(range(100, 5100))
+    return fan(range(21), adj, nv)
+
+
+def sparse_rows():
+    """Degree-1 rows with runs of degree-0 rows between them: 703 entries (more than 256) share chunk 0 with a row of
+    degree K_CHUNK - 351 = 1697, and a run of 300 degree-0 frontier rows straddles the boundary of chunks 0 and 1
+    (positions 2047 | 2048 belong to the rows before and after the run). Both are asserted from the chunk map."""
+    nv = 4000
+    adj, r, pos = {}, 0, 0
+    rnd = random.Random(3)
+    for k in range(350):                                          # 350 degree-1 rows, each followed by a degree-0 row
+        adj[r] = [rnd.randrange(nv)]
+        r += 2
+        pos += 1
+    adj[r] = rnd.sample(range(nv), K_CHUNK - pos - 1)             # fills chunk 0 up to position 2046
+    r += 1
+    adj[r] = [rnd.randrange(nv)]                                  # position 2047, the last of chunk 0
+    r += 301                                                      # the run of 300 empty rows
+    adj[r] = [rnd.randrange(nv)]                                  # position 2048, the first of chunk 1
+    r += 1
+    for k in range(300):
+        adj[r] = [rnd.randrange(nv)]
+        r += 1 + k % 3
+    assert r < nv
+    g, seeds = fan(range(r), adj, nv)
+    ends = chunk_ends(g, list(range(1, r + 1)), [1])
+    (b0, _), (e0, _) = ends[0]
+    (b1, _), _ = ends[1]
+    assert b0 == 0 and e0 - b0 + 1 > 256 and b1 - e0 == 301, ends[:2]   # 703 entries in chunk 0; 300 empty rows between
+    assert all(i not in adj for i in range(e0 + 1, b1)) and len(adj[700]) == K_CHUNK - 351
+    return g, seeds
+
+
+def chunk_ends(graph, frontier, over):
+    """The chunk map of a hop over `frontier` (vids in row order): per K_CHUNK chunk of the hop's edges, the (frontier
+    index, slot) of its first and of its last edge; the entries run vertex by vertex, slot by slot."""
+    ends, pos = [], 0
+    owner = []                                                    # (first position, count, index, slot) per entry
+    for i, v in enumerate(frontier):
+        for k, t in enumerate(over):
+            n = len(graph.rows().get((v, t), ()))
+            if n:
+                owner.append((pos, n, i, k))
+            pos += n
+    at = 0
+    for c in range((pos + K_CHUNK - 1) // K_CHUNK):
+        lo, hi = c * K_CHUNK, min(pos, (c + 1) * K_CHUNK) - 1
+        while owner[at][0] + owner[at][1] <= lo:
+            at += 1
+        j = at
+        while owner[j][0] + owner[j][1] <= hi:
+            j += 1
+        ends.append((owner[at][2:], owner[j][2:]))
+    return ends
+
+
+SLOT_DEGREES = ((1, 500), (2, 700), (3, 300))
+
+
+def interleaved_slots(empty_type=None):
+    """Three OVER types (e, f, g) whose per-vertex entries interleave: each of 8 frontier rows has 500 edges of e, 700 of
+    f and 300 of g (1500 a row), so the chunk boundaries fall in different slots: chunk 2 (positions 4096 .. 6143) begins
+    in slot f (slot 1) of row 2 and ends in slot e (slot 0) of row 4, which is asserted here from the chunk map. With
+    empty_type that type has a slot pair and no edge at all (the other slots' boundaries move; nothing is asserted of
+    them)."""
+    nv = 800
+    rnd = random.Random(11)
+    adj = {}
+    for r in range(8):
+        lst = []
+        for t, n in SLOT_DEGREES:
+            if t != empty_type:
+                lst += [(d, t, 0) for d in rnd.sample(range(nv), n)]
+        adj[r] = lst
+    g, seeds = fan(range(8), adj, nv, types=[1, 2, 3])
+    if empty_type is None:
+        ends = chunk_ends(g, list(range(1, 9)), [1, 2, 3])
+        assert ends[2] == ((2, 1), (4, 0)), ends                  # begins in slot 1 of one vertex, ends in slot 0 of another
+        assert {b[1] for b, _ in ends} >= {0, 1} and len(ends) == 6
+    return g, seeds
+
+
+def seed_graph(nv=1500, types=(1,), seed=5):
+    """nv vertices with scattered vids; degree 0 .. 2 per type, so that with several types some vertices have edges in
+    no slot, some in one and some in all."""
+    rnd = random.Random(seed)
+    vids = sorted(rnd.sample(range(10, 20 * nv), nv))
+    edges = []
+    for i, v in enumerate(vids):
+        for t in types:
+            if (i + t) % 5 == 0 or i % 7 == 0:                    # i % 7 == 0: degree 0 in all slots
+                continue
+            for d in rnd.sample(vids, 1 + (i + t) % 2):
+                edges.append(edge(v, d, t, 0))
+    return Graph(vids, edges, types=list(types))
+
+
+def vid_width_graph():
+    """Vids that need 1, 2, 4 and 8 bytes, negative ones among them, each with a present neighbour in vid order and a
+    missing vid next to it."""
+    vids = [-(1 << 40), -70000, -300, -2, -1, 1, 2, 100, 127, 128, 300, 32767, 32768, 70000, (1 << 31) - 1, 1 << 31,
+            (1 << 40) + 7, INT64_MAX - 1]
+    rnd = random.Random(9)
+    edges = []
+    for v in vids:
+        for d in rnd.sample(vids, 3):
+            edges.append(edge(v, d, 1, 0))
+    return Graph(vids, edges)
+
+
+def sparse_graph(n, kind="spread"):
+    """A hop of exactly n edges for the sparse kernel. spread: destinations at random; one: every edge to one row;
+    distinct: every destination different (the next frontier equals the edges)."""
+    rnd = random.Random(50 + n)
+    nv = max(n, 16) + 64
+    adj, left, r = {}, n, 0
+    dsts = list(range(nv))
+    rnd.shuffle(dsts)
+    while left:
+        d = min(left, rnd.choice([1, 1, 2, 5, 40, 200]))
+        if kind == "one":
+            d = 1
+            adj[r] = [nv - 3]
+        elif kind == "distinct":
+            adj[r] = [dsts.pop() for _ in range(d)]
+        else:
+            adj[r] = rnd.sample(range(nv), d)
+        left -= d
+        r += 1
+    return fan(range(r), adj, nv)
+
+
+def sparse_repeats():
+    """One destination (row 900) once in every 256-edge slice of chunk 0 and once in each of chunks 0, 1 and 2; every
+    other destination distinct."""
+    nv = 3 * K_CHUNK + 1100
+    per = K_CHUNK // K_SPARSE_SUB
+    adj = {}
+    nxt = iter(range(1000, nv))
+    for k in range(3 * K_SPARSE_SUB):                             # row k owns slice k: 256 edges
+        hit = k < K_SPARSE_SUB or k % K_SPARSE_SUB == 3
+        adj[k] = ([900] if hit else []) + [next(nxt) for _ in range(per - (1 if hit else 0))]
+    return fan(range(3 * K_SPARSE_SUB), adj, nv)
+
+
+def pull_degrees(frontier_share=2, seed=0):
+    """Targets with in-degree 0, 1, 1, 15, 16, 17, 1023, 1024, 1025 and 3000 (rows 0 .. 9; the two of in-degree 1 differ
+    in whether their source is in the frontier: row 10 is in it, row 11 is not, both asserted), the other sources drawn
+    from rows 10 .. 3009; every target has two out-edges for the hop after the pull. The frontier is one source row in
+    `frontier_share` (at least 2)."""
+    rnd = random.Random(70 + seed)
+    degs = [0, 1, 1, 15, 16, 17, K_PULL_SEG - 1, K_PULL_SEG, K_PULL_SEG + 1, 3000]
+    pool = list(range(10, 3010))
+    nv = 3040
+    adj = {}
+    for t, d in enumerate(degs):
+        for s in (pool if d == len(pool) else [pool[t - 1]] if d == 1 else rnd.sample(pool, d)):
+            adj.setdefault(s, []).append(t)
+        adj[t] = [3010 + t, 3011 + t]
+    front = [s for k, s in enumerate(pool) if k % frontier_share == 0]
+    assert 1 in adj[pool[0]] and 2 in adj[pool[1]] and pool[0] in front and pool[1] not in front
+    assert [sum(1 for lst in adj.values() if t in lst) for t in range(10)] == degs
+    return fan(front, adj, nv)
+
+
+PULL_WHICH = ("head_first", "head_last", "past_head", "segment_last", "segment_first")
+
+
+def pull_single(which):
+    """Row T (the last but the seed) of in-degree 2100 (three K_PULL_SEG segments) whose only in-neighbour in the
+    frontier is, as the pull kernel orders the in-list, PULL_WHICH: the first head entry (the source with the largest
+    out-degree), the last head entry (the smallest out-degree among the K_PULL_K largest), the first source past the head
+    (the 17th by out-degree), or the source at position K_PULL_SEG - 1 / K_PULL_SEG of the stored in-list (key order:
+    the source vids' little-endian bytes): the last entry of segment 0 / the first of segment 1. Head source k has
+    out-degree 19 - k, the 17th has 3, every other source 1; the extra edges go to filler rows. Forty decoy rows with
+    one edge each to fillers are in the frontier too, so that the hop has enough edges to be pulled.
+    Returns (Graph, seeds, T's vid)."""
+    D = 2100
+    nv = D + 120
+    T = nv - 1
+    order = sorted(range(D), key=lambda r: _key(r + 1))            # the stored in-list of T
+    seg_last, seg_first = order[K_PULL_SEG - 1], order[K_PULL_SEG]
+    head = [r for r in range(100, 400, 17) if r not in (seg_last, seg_first)][:K_PULL_K]
+    past = next(r for r in range(500, 600) if r not in (seg_last, seg_first))
+    assert len(head) == K_PULL_K
+    fill = list(range(D, D + 30))
+    adj = {r: [T] for r in range(D)}
+    for k, r in enumerate(head):
+        adj[r] = fill[:18 - k] + [T]
+    adj[past] = fill[:2] + [T]
+    decoys = list(range(D + 40, D + 80))
+    for k, r in enumerate(decoys):
+        adj[r] = [fill[k % 30]]
+    adj[T] = [fill[0], fill[1], fill[2]]
+    chosen = {"head_first": head[0], "head_last": head[-1], "past_head": past, "segment_last": seg_last,
+              "segment_first": seg_first}[which]
+    g, seeds = fan([chosen] + decoys, adj, nv)
+    return g, seeds, T + 1
+
+
+def pull_ring(nv, types=(1,), seed=0):
+    """nv rows, every one with an in-edge of every type (a ring per type, plus random chords); a third of the rows in
+    the frontier. The seed row has no in-edge, so the pull's image holds exactly nv rows."""
+    rnd = random.Random(90 + nv + seed)
+    adj = {}
+    for r in range(nv):
+        for t in types:
+            ds = {(r + t) % nv}
+            if rnd.random() < 0.4:
+                ds.add(rnd.randrange(nv))
+            adj.setdefault(r, []).extend((d, t, 0) for d in sorted(ds))
+    return fan(rnd.sample(range(nv), max(nv // 3, 2)), adj, nv, types=list(types))
+
+
+COMPACT_REACHED = ("none", "all", "first", "last", "edges")
+
+
+COMPACT_SEED_ROW = 5
+
+
+def compaction_graph(nv, kind):
+    """nv rows in all; the seed is row 5 (vid 6) and its out-edges reach exactly the rows COMPACT_REACHED names: none,
+    all (itself too), row 0, the last row, or rows 1023, 1024, 4095 and 4096 (those the table has): the ends of a
+    wave's 1024-row run and of a K_COMPACT_TILE tile. The compaction after hop 1 lists them. Up to four reached rows
+    get 90 out-edges each, so that hop 2 has at least nv / 100 edges for every nv up to 9000 and can be pulled (it then
+    reads the bitmap, whose last word's last bit is the last row); more reached rows get one or two. The seed gets no
+    edge beyond those that reach."""
+    seed = COMPACT_SEED_ROW
+    reached = {"none": [], "all": list(range(nv)), "first": [0], "last": [nv - 1],
+               "edges": [r for r in (1023, 1024, K_COMPACT_TILE - 1, K_COMPACT_TILE) if r < nv]}[kind]
+    assert kind == "all" or seed not in reached
+    edges = [edge(seed + 1, r + 1) for r in reached]
+    for r in reached:
+        ds = range(r + 1, r + 91) if len(reached) <= 4 else {(r * 13 + 1), (r * 29 + 5)}
+        for d in sorted({x % nv for x in ds}):
+            if r != seed:                                         # (the seed's own edges are the ones above)
+                edges.append(edge(r + 1, d + 1))
+    assert len(reached) > 4 or not reached or 90 * 100 >= nv
+    return Graph(range(1, nv + 1), edges), [seed + 1]
+
+
+RANK_FORMS = {
+    "zero": [0], "five": [5], "minus1": [-1], "int8": [-128, 127, 0], "int16": [-32768, 32767, 0, 200],
+    "int32": [-(1 << 31), (1 << 31) - 1, 0, 70000], "int64": [INT64_MIN, INT64_MAX, 0, 1 << 40],
+}
+B_SETS = {
+    "i8": [-128, 127], "i8x": [-129, 128], "i32": [-(1 << 31), (1 << 31) - 1], "i32x": [-(1 << 31) - 1, 1 << 31],
+    "i64": [INT64_MIN, INT64_MAX],
+}
+
+
+def storage_graph(rank_e, rank_f, b_set, seed=0):
+    """Two OVER types in different storage forms. Type e: every dst vid fits int8 (rows 1 .. 100); type f: one dst vid
+    is 2^31 + 5 (the last vertex), so its dst column stays wide. Ranks of e / f cycle through RANK_FORMS[rank_e / rank_f]
+    with every value present; parallel edges that differ only in rank where the form has several values. Column b of
+    both types holds exactly the values of B_SETS[b_set]. GO 2 STEPS from the hub (vid 120)."""
+    rnd = random.Random(seed + 17)
+    big = (1 << 31) + 5
+    vids = list(range(1, 101)) + [120, big]
+    edges = []
+    re_, rf = RANK_FORMS[rank_e], RANK_FORMS[rank_f]
+    bs = B_SETS[b_set]
+    n = [0]
+
+    have = set()
+
+    def add(a, d, t, r):
+        if (a, d, t, r) in have:
+            return
+        have.add((a, d, t, r))
+        p = default_props(a, d, t, r)
+        edges.append(edge(a, d, t, r, (p[0], p[1], bs[n[0] % len(bs)])))
+        n[0] += 1
+
+    front = list(range(1, 61))
+    for k, v in enumerate(front):
+        add(120, v, 1, re_[k % len(re_)])
+    for k, v in enumerate(front):
+        ds = rnd.sample(range(1, 101), 4)
+        for j, d in enumerate(ds):
+            add(v, d, 1, re_[(k + j) % len(re_)])
+        if len(re_) > 1:                                          # parallel edges that differ only in rank
+            for r in re_:
+                add(v, ds[0], 1, r)
+        for j, d in enumerate(rnd.sample(range(1, 101), 3) + ([big] if k % 9 == 0 else [])):
+            add(v, d, 2, rf[(k + j) % len(rf)])
+        if len(rf) > 1 and k % 4 == 0:
+            d = 1 + (v * 7) % 100
+            for r in rf:
+                add(v, d, 2, r)
+    g = Graph(vids, edges, types=[1, 2])
+    for t, form in ((1, re_), (2, rf)):
+        assert {x[3] for x in g.edges if x[2] == t} == set(form), (t, form)
+    assert {x[4][2] for x in g.edges} == set(bs)
+    return g, [120]
+
+
+def resv_arrays(rows, nsuper=4):
+    """The row-reservation CSR, built with numpy: `nsuper` supernodes (rows 0 .. nsuper - 1) with `rows` out-edges of
+    type e in all, to rows spread over the table; the seed (the last row) points at the supernodes. A final hop from
+    the supernodes returns exactly `rows` rows without WHERE; p0 is the CSR position's parity, so `p0 < 1` keeps every
+    second row. Returns (vpart, vid, slots, model columns): the columns (dst, rank, p0, p1) of the final hop's rows."""
+    nv = max(rows // nsuper + nsuper + 2, 64)
+    per = [rows // nsuper + (1 if k < rows % nsuper else 0) for k in range(nsuper)]
+    assert max(per) <= nv - 1
+    off = np.zeros(nv + 1, np.uint64)
+    off[1:nsuper + 1] = np.cumsum(per)
+    off[nsuper + 1:nv] = rows
+    off[nv] = rows + nsuper
+    dst_rows = np.concatenate([np.arange(p, dtype=np.int64) for p in per] + [np.arange(nsuper, dtype=np.int64)])
+    src_rows = np.concatenate([np.full(p, k, np.int64) for k, p in enumerate(per)] + [np.full(nsuper, nv - 1, np.int64)])
+    # key order inside a row: by the dst vid's little-endian bytes
+    dvid = dst_rows + 1
+    key = dvid.astype(np.uint64).byteswap()
+    order = np.lexsort((key, src_rows))
+    src_rows, dst_rows, dvid = src_rows[order], dst_rows[order], dvid[order]
+    pos = np.arange(len(dvid), dtype=np.int64)
+    p0 = pos % 2
+    p1 = (pos * 6364136223846793005 + 1442695040888963407) % (1 << 40) - (1 << 39)
+    b = pos % 200 - 100
+    out = (1, off, dvid, [p0, p1, b], np.zeros(len(dvid), np.int64))
+    # the exact mirror: in-edges of every row, sources in key order
+    skey = (src_rows + 1).astype(np.uint64).byteswap()
+    iorder = np.lexsort((skey, dst_rows))
+    ioff = np.zeros(nv + 1, np.uint64)
+    ioff[1:] = np.cumsum(np.bincount(dst_rows, minlength=nv))
+    inn = (-1, ioff, (src_rows + 1)[iorder], [p0[iorder], p1[iorder], b[iorder]], np.zeros(len(dvid), np.int64))
+    final = slice(0, rows)                                        # the supernodes' edges: the final hop's rows
+    cols = [dvid[final], np.zeros(rows, np.int64), p0[final], p1[final]]
+    return np.ones(nv, np.int32), np.arange(1, nv + 1, dtype=np.int64), [out, inn], cols, nv
+
+
+def resv_graph(rows, nsuper=4):
+    """The same graph as a Graph (for the model and the oracle)."""
+    vpart, vid, slots, cols, nv = resv_arrays(rows, nsuper)
+    _, off, dvid, (p0, p1, b), _ = slots[0]
+    src = np.repeat(np.arange(1, nv + 1), np.diff(off.astype(np.int64)))
+    edges = [(int(s), int(d), 1, 0, (int(x), int(y), int(z))) for s, d, x, y, z in zip(src, dvid, p0, p1, b)]
+    return Graph(range(1, nv + 1), edges), [nv]
+
+
+# ----------------------------------------------------------------------------- the cases
+# Shared by tests/test_gpu_go_shapes.py (which runs them on the device) and tests/test_goref_host.py (which shows the
+# model equal to the oracle on every one of them). A case: a graph builder and the queries run on it.
+Query = namedtuple("Query", "form over direction m n seeds pushdown")
+
+
+def Q(form, over=("e",), direction=FORWARD, m=None, n=2, seeds=None, pushdown=True):
+    return Query(form, tuple(over), direction, m, n, tuple(seeds) if seeds is not None else None, pushdown)
+
+
+Case = namedtuple("Case", "build queries kv")
+CASES = {}
+_built = {}
+
+
+def case(name, build, queries, kv=False):
+    CASES[name] = Case(build, queries, kv)
+
+
+def built(name):
+    """(Graph, default seeds) of a case, built once."""
+    if name not in _built:
+        _built[name] = CASES[name].build()[:2]
+    return _built[name]
+
+
+_models = {}
+
+
+def case_model(name, q):
+    """The model of one query of a case, computed once and shared."""
+    if (name, q) not in _models:
+        g, seeds = built(name)
+        _models[(name, q)] = model(g, q.form, q.seeds if q.seeds is not None else seeds, q.over, q.direction, q.m, q.n,
+                                   q.pushdown)
+    return _models[(name, q)]
+
+
+def case_sentence(name, q):
+    g, seeds = built(name)
+    return sentence(q.form, q.seeds if q.seeds is not None else seeds, q.over, q.direction, q.m, q.n)
+
+
+def _repeat(vids, n):
+    return [vids[(k * 7) % len(vids)] for k in range(n)]
+
+
+def _seed_case(types, counts, form):
+    g = seed_graph(types=types)
+    over = [NAME_OF[t] for t in types]
+    qs = [Q(form, over, n=2, seeds=_repeat(g.vids, c)) for c in counts]
+    qs.append(Q(form, over, n=1, seeds=list(g.vids)))                              # every vertex, the seed hop records
+    missing = [v + d for v in g.vids[::50] for d in (-1, 1) if v + d not in set(g.vids)]
+    qs.append(Q(form, over, n=2, seeds=[x for v in missing for x in (v, v + 1 if v + 1 in set(g.vids) else v - 1)]))
+    qs.append(Q(form, over, n=2, seeds=[g.vids[3], g.vids[8], g.vids[3]]))         # the same seed twice
+    qs.append(Q("distinct", over[:1], n=2, seeds=[g.vids[3], g.vids[8], g.vids[3]]))
+    qs.append(Q(form, over, n=2, seeds=[g.vids[0], g.vids[7], g.vids[14]]))        # degree 0 in all slots
+    qs.append(Q(form, over, m=1, n=3, seeds=g.vids[1:40]))
+    return lambda: (g, [g.vids[1]]), qs
+
+
+# seed hop: seeds x slots = 1, 4095, 4096, 4097 entries with one OVER type; 3, 4095 and 4098 with three (1365 and 1366
+# seeds: 4096 is no multiple of 3)
+case("seed1", *_seed_case((1,), [1, K_SEED_FUSE_MAX - 1, K_SEED_FUSE_MAX, K_SEED_FUSE_MAX + 1], "bench"))
+case("seed3", *_seed_case((1, 2, 3), [1, (K_SEED_FUSE_MAX - 1) // 3, K_SEED_FUSE_MAX // 3 + 1], "multi_all"))
+
+
+def _vid_case():
+    g = vid_width_graph()
+    have = set(g.vids)
+    seeds = []
+    for v in g.vids:
+        seeds.append(v)
+        seeds += [w for w in (v - 1, v + 1) if w not in have and INT64_MIN <= w <= INT64_MAX]
+    return g, seeds
+
+
+case("vids", _vid_case, [Q("keys", n=1), Q("keys", n=2), Q("bench", n=2), Q("keys", direction=REVERSELY, n=2),
+                         Q("keys", direction=BIDIRECT, n=2), Q("keys", direction=BIDIRECT, m=1, n=2)])
+
+CHUNK_SIZES = (1, K_CHUNK - 1, K_CHUNK, K_CHUNK + 1, 3 * K_CHUNK + 5)
+for _n in CHUNK_SIZES:
+    case("chunk%d" % _n, (lambda n: lambda: frontier_edges(n))(_n), [Q("bench", n=2), Q("all", n=2), Q("all", n=3)])
+case("chunk_supernode", supernode_midchunk, [Q("bench", n=2), Q("all", n=3)])
+case("chunk_sparse_rows", sparse_rows, [Q("bench", n=2), Q("keys", n=2), Q("all", n=3)])
+case("chunk_slots", interleaved_slots, [Q("multi_all", "efg", n=2), Q("multi", "efg", n=2, pushdown=False),
+                                        Q("multi_all", "efg", n=3)])
+case("chunk_empty_slot", lambda: interleaved_slots(empty_type=3),
+     [Q("multi_all", "efg", n=2), Q("multi_all", "gfe", n=2), Q("multi_all", "efg", n=3)])
+
+SPARSE_SIZES = (255, 256, 257, K_CHUNK - 1, K_CHUNK, K_CHUNK + 1)
+for _n in SPARSE_SIZES:
+    case("sparse%d" % _n, (lambda n: lambda: sparse_graph(n))(_n), [Q("all", n=3), Q("distinct", n=4)])
+case("sparse_one", lambda: sparse_graph(K_CHUNK + 1, "one"), [Q("all", n=3)])
+case("sparse_distinct", lambda: sparse_graph(K_CHUNK + 1, "distinct"), [Q("all", n=3)])
+case("sparse_repeats", sparse_repeats, [Q("all", n=3)])
+case("sparse_empty", lambda: fan(range(40), {}, 100), [Q("all", n=3)])
+case("sparse_after_pull", lambda: pull_ring(600), [Q("all", n=3), Q("bench", n=4)])
+
+case("pull_degrees", lambda: pull_degrees(2), [Q("all", n=3), Q("bench", n=3)])
+case("pull_degrees_thin", lambda: pull_degrees(60), [Q("all", n=3)])
+for _w in PULL_WHICH:
+    case("pull_" + _w, (lambda w: lambda: pull_single(w))(_w), [Q("all", n=3)])
+PULL_V = (63, 64, 65, K_PULL_WINDOW - 1, K_PULL_WINDOW, K_PULL_WINDOW + 1)
+for _n in PULL_V:
+    case("pull_v%d" % _n, (lambda n: lambda: pull_ring(n))(_n), [Q("all", n=3)])
+case("pull_4types", lambda: pull_ring(300, (1, 2, 3, 4)), [Q("multi_all", "efgh", n=3)])
+case("pull_5types", lambda: pull_ring(300, (1, 2, 3, 4, 5)), [Q("multi_all", "efghi", n=3)])
+
+COMPACT_V = (K_COMPACT_TILE - 1, K_COMPACT_TILE, K_COMPACT_TILE + 1, 2 * K_COMPACT_TILE + 1)
+for _n in COMPACT_V:
+    for _k in COMPACT_REACHED:
+        case("compact%d_%s" % (_n, _k), (lambda n, k: lambda: compaction_graph(n, k))(_n, _k), [Q("all", n=3)])
+
+STORAGE = (("zero", "int8", "i8"), ("five", "int16", "i8x"), ("minus1", "int32", "i32"), ("int64", "zero", "i32x"),
+           ("int8", "int64", "i64"), ("int16", "five", "i64"))
+for _c in STORAGE:
+    case("storage_%s_%s_%s" % _c, (lambda c: lambda: storage_graph(*c))(_c),
+         [Q("multi_all", "ef", n=2), Q("multi", "ef", n=2), Q("multi", "fe", n=2, pushdown=False), Q("signed", "e", n=2), Q("signed", "f", n=2), Q("keys", "e", n=2),
+          Q("bench", "e", n=2)])
+
+
+def _tag_case():
+    g, seeds = frontier_edges(300, seed=4)
+    g.tags = {v: (v * 37) % 1000 - 300 for v in g.vids if v % 3}           # a third of the vertices lack the tag
+    return g, seeds
+
+
+case("tags", _tag_case, [Q("tags", n=2), Q("tags", m=1, n=2)], kv=True)
+
+RESV_ROWS = ((1 << K_RESV_SHIFT) - 1, 1 << K_RESV_SHIFT, (1 << K_RESV_SHIFT) + 1, K_RESV_GROUPS * (1 << K_RESV_SHIFT) + 1)
