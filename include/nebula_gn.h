@@ -708,6 +708,71 @@ int32_t ngx_fetch(ngx_ctx* ctx, const ngx_go_result* r, const ngx_fetch_plan* pl
 int32_t ngx_go_fetch(ngx_ctx* ctx, const ngx_go_plan* go, const ngx_fetch_plan* plan, ngx_fetch_result** out);
 void ngx_fetch_result_free(ngx_fetch_result* r);
 
+/* ---------------------------------------------------------------- LOOKUP ON a tag / an edge type */
+/* `LOOKUP ON <tag|edge> WHERE ... [YIELD ...]` as one streaming pass over the stored columns: replaces
+ * StorageClient::lookUpIndex (LookUpIndexProcessor::process: IndexExecutor::executeExecutionPlan's range scan of the
+ * index keys, conditionsCheck and getVertexRow / getEdgeRow, src/storage/index/). No index is stored: the caller
+ * (nebula_amd/lookup.py restates LookupExecutor and IndexPolicyMaker) hands the plan the chosen index yields.
+ *   fields  the index fields the scan bounds, in index order. INT / TIMESTAMP / FLOAT / DOUBLE: [lo, hi) in the
+ *           encoded-key domain (the field's 8 big-endian index key bytes read as a u64; lo == hi: key == lo, the
+ *           reference's prefix scan). BOOL / STRING: an equality constant (bits / str).
+ *   terms   the residual filter (requiredFilter_): `field op constant` per conjunct, evaluated with
+ *           RelationalExpression::eval's typing (bool -> int -> double; a string against a non-string fails the row;
+ *           == and != on doubles within 1e-8) over the value as decodeVariant(encodeVariant(v)) returns it.
+ *   yields  field names of the schema.
+ * A tag is scanned over the rows of its table, an edge type over its out-slot (an edge is indexed under its
+ * positive type only). Output columns: the vid (VID), or src (VID), dst (VID), rank (INT), then the yields; rows in
+ * storage order; the output is sized exactly by a count pass.
+ * NGX_E_UNSUPPORTED with a reason starting "lookup:" (ngx_last_error), decided before any launch, for: a TTL tag or
+ * edge schema, an edge slot holding edges with empty or unreadable values, a field, term or yield column some
+ * row's schema version lacks, more than 16 fields, terms or columns, world > 1; and, after the keep and scan passes
+ * have counted the rows and before the emit, for an output above flag lookup_rows_max. There is no host path behind
+ * it: the caller reports the refusal.
+ * Flags: "lookup_device" (read-only) counts the calls completed; "lookup_grid_max" (0, the default: built-in 2048,
+ * else 1 .. 2048) caps the workgroups of the keep and emit kernels: same rows in the same order under every
+ * setting; "lookup_rows_max" (default 2^26) the most output rows. ngx_kernel_stats: launch groups "lookup_keep",
+ * "lookup_scan", "lookup_emit". */
+#define NGX_LK_INT 0
+#define NGX_LK_DOUBLE 1
+#define NGX_LK_BOOL 2
+#define NGX_LK_STRING 3
+typedef struct {
+    const char* field;                 /* the schema field */
+    int32_t kind;                      /* NGX_LK_* of the constant */
+    int32_t op;                        /* terms: 0 <, 1 <=, 2 >, 3 >=, 4 ==, 5 != (field op constant) */
+    uint64_t lo, hi;                   /* fields of a numeric type: the key range */
+    int64_t bits;                      /* BOOL field: 0 / 1; terms: the int64 / double bits / 0, 1 */
+    const char* str;                   /* NGX_LK_STRING: the constant's bytes */
+    uint64_t str_len;
+} ngx_lookup_cond;
+typedef struct {
+    int32_t space;
+    int32_t is_edge;
+    int32_t schema_id;                 /* the tag id, or the edge type (> 0) */
+    int32_t nfields;
+    const ngx_lookup_cond* fields;
+    int32_t nterms;
+    const ngx_lookup_cond* terms;
+    int32_t nyields;
+    const char* const* yields;
+} ngx_lookup_plan;
+typedef struct {
+    int32_t code;
+    int32_t ncols;
+    const int32_t* col_types;          /* NGX_T_* per column */
+    uint64_t nrows;
+    const ngx_cell* cells;             /* cells[row * ncols + col] */
+    const char* strings;
+    uint64_t strings_len;
+    uint64_t scanned_rows;             /* rows of the tag table / edges of the slot the keep pass read */
+    uint64_t keep_bytes;               /* bytes the keep pass reads: rows * the conditions' stored widths (present[]
+                                        * for a tag); a STRING condition counts 8 bytes, not the bytes compared, and
+                                        * a row rejected early reads less: a rough figure */
+    double device_ms;                  /* HIP-event time of the call, plan upload to the last cell */
+} ngx_lookup_result;
+int32_t ngx_lookup(ngx_ctx* ctx, const ngx_lookup_plan* plan, ngx_lookup_result** out);
+void ngx_lookup_result_free(ngx_lookup_result* r);
+
 /* ---------------------------------------------------------------- FIND SHORTEST PATH
  * `FIND SHORTEST PATH FROM <vids> TO <vids> OVER <edges> [REVERSELY] [UPTO n STEPS]` (FindPathExecutor,
  * src/graph/FindPathExecutor.cpp) searched in HBM: breadth-first levels from the sources over the sentence's edge

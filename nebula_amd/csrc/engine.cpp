@@ -260,6 +260,12 @@ struct ngx_ctx {
     DBuf fxRow, fxEidx, fxHits, fxCount, fxBase, fxTiles, fxSeen, fxDesc, fxKeys[3], fxSlen, fxSpre, fxCells, fxStr;
     uint64_t fetchDevice = 0;                           // calls completed on the device (flag fetch_device)
     uint32_t fetchGridMax = 0;                          // flag fetch_grid_max: most workgroups of a sweep, 0: built-in
+    // ngx_lookup: per row its keep byte; per 256-row chunk the kept rows and their scan; the plan's conditions, string
+    // constants and yield descriptors; string lengths and their scan; output cells and bytes
+    DBuf lkKeep, lkCount, lkBase, lkTiles, lkConds, lkPool, lkYs, lkSlen, lkSpre, lkCells, lkStr;
+    uint64_t lookupDevice = 0;                          // calls completed (flag lookup_device)
+    uint32_t lookupGridMax = 0;                         // flag lookup_grid_max: most workgroups of a sweep, 0: built-in
+    int64_t lookupRowsMax = int64_t(1) << 26;           // flag lookup_rows_max: the most output rows
     // ngx_go_set: the string arenas of the left traversal while the right one runs on the second lane
     std::vector<DBuf> setArena;
     // flag set_check_left (debug): ngx_go_set digests the left result before and after the right traversal
@@ -2190,6 +2196,17 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
         c->fetchGridMax = static_cast<uint32_t>(value);
         return NGX_OK;
     }
+    if (n == "lookup_grid_max") {
+        if (value < 0 || value > static_cast<int64_t>(kLookupGridMax))
+            return fail(c, NGX_E_BAD_ARGUMENT, "lookup_grid_max: 0 (built-in) or 1 .. " + std::to_string(kLookupGridMax));
+        c->lookupGridMax = static_cast<uint32_t>(value);
+        return NGX_OK;
+    }
+    if (n == "lookup_rows_max") {
+        if (value < 0) return fail(c, NGX_E_BAD_ARGUMENT, "lookup_rows_max: >= 0");
+        c->lookupRowsMax = value;
+        return NGX_OK;
+    }
     if (n == "set_grid_max") {
         if (value < 0 || value > static_cast<int64_t>(kSetGridMax))
             return fail(c, NGX_E_BAD_ARGUMENT, "set_grid_max: 0 (built-in) or 1 .. " + std::to_string(kSetGridMax));
@@ -2288,6 +2305,9 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "set_grid_max") *value = c->setGridMax;
     else if (n == "fetch_grid_max") *value = c->fetchGridMax;
     else if (n == "fetch_device") *value = static_cast<int64_t>(c->fetchDevice);
+    else if (n == "lookup_grid_max") *value = c->lookupGridMax;
+    else if (n == "lookup_rows_max") *value = c->lookupRowsMax;
+    else if (n == "lookup_device") *value = static_cast<int64_t>(c->lookupDevice);
     else if (n == "set_loop_flushes") *value = static_cast<int64_t>(c->setLoopFlushes);
     else if (n == "group_grid_max") *value = c->groupGridMax;
     else if (n == "order_grid_max") *value = c->orderGridMax;
@@ -7128,6 +7148,225 @@ extern "C" int32_t ngx_go_fetch(ngx_ctx* c, const ngx_go_plan* go, const ngx_fet
     R->r.code = rc;
     *out = &R.release()->r;
     return rc;
+}
+
+// ------------------------------------------------------------------------ LOOKUP ON (ngx_lookup)
+namespace {
+
+struct LookupResultHolder {
+    ngx_lookup_result r{};
+    std::vector<int32_t> colTypes;
+    std::vector<ngx_cell> cells;
+    std::string strings;
+};
+
+int32_t lookupKindOf(int32_t t) {
+    switch (t) {
+        case NGX_T_BOOL: return kLkBool;
+        case NGX_T_INT: case NGX_T_VID: case NGX_T_TIMESTAMP: return kLkInt;
+        case NGX_T_FLOAT: case NGX_T_DOUBLE: return kLkDouble;
+        case NGX_T_STRING: return kLkString;
+        default: return -1;
+    }
+}
+
+// Every refusal but one is decided before the first launch; an output above lookup_rows_max is known only after
+// the keep and scan passes and is refused before the emit. Nothing enumerates the Engine's rows on the host, so a
+// refusal is the caller's error: there is no host leg to fall back to (FETCH has one).
+// keep_bytes is the columns' stored widths times the rows scanned: an upper estimate for fixed-width columns (a row
+// rejected by an earlier condition does not read the later ones) and a lower one for a STRING condition, which
+// counts its two offsets' 8 bytes and not the string bytes compared.
+int32_t lookupOp(ngx_ctx* c, const ngx_lookup_plan* p, LookupResultHolder& R) {
+    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "lookup: world > 1 needs every shard's rows concatenated");
+    Space* spp = findSpace(c, p->space);
+    if (!spp || !spp->dev) return fail(c, NGX_E_NOT_LOADED, "space not committed");
+    const Space& sp = *spp;
+    const DeviceGraph& d = *sp.dev;
+    const bool edge = p->is_edge != 0;
+    const int nkey = edge ? 3 : 1;
+    if (p->nfields < 0 || p->nterms < 0 || p->nyields < 0) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: negative count");
+    if (p->nfields > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 scanned fields");
+    if (p->nterms > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 residual terms");
+    if (p->nyields + nkey > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 columns");
+    if ((p->nfields && !p->fields) || (p->nterms && !p->terms) || (p->nyields && !p->yields))
+        return fail(c, NGX_E_BAD_ARGUMENT, "lookup: array missing");
+    const SchemaSet* ss = edge ? sp.edge(p->schema_id) : sp.tag(p->schema_id);
+    if (!ss || (edge && p->schema_id <= 0)) return fail(c, NGX_E_QUERY, edge ? "Unknown error(407): " : "Unknown error(406): ");
+    int32_t tcol;
+    int64_t tdur;
+    if (ttlInfo(ss, tcol, tdur)) return fail(c, NGX_E_UNSUPPORTED, edge ? "lookup: a TTL edge schema" : "lookup: a TTL tag schema");
+    const int32_t slot = edge ? sp.slotOf(p->schema_id) : sp.tagSlotOf(p->schema_id);
+    if (edge && slot >= 0 && d.slots[slot].hasFlags) return fail(c, NGX_E_UNSUPPORTED, "lookup: edges with empty or unreadable values");
+    const int32_t colBase = slot < 0 ? 0 : edge ? d.slots[slot].colBase : d.tags[slot].colBase;
+    auto column = [&](const char* name, DCol& col, int32_t& type) -> int32_t {
+        const std::string field = name ? name : "";
+        const int32_t fi = ss->latest().index(field);
+        if (fi < 0) return fail(c, NGX_E_QUERY, "Unknown column `" + field + "' in schema");
+        type = ss->latest().fields[fi].type;
+        if (lookupKindOf(type) < 0) return fail(c, NGX_E_UNSUPPORTED, "lookup: a column of an unknown type");
+        col = DCol{};
+        if (slot >= 0) {
+            col = d.cols[colBase + fi];
+            if (col.valid) return fail(c, NGX_E_UNSUPPORTED, "lookup: field `" + field + "' is missing from some row's schema version");
+        }
+        return NGX_OK;
+    };
+    std::vector<LookupCond> conds(p->nfields + p->nterms);
+    std::string pool;
+    uint64_t rowBytes = edge ? 0 : 1;                             // present[]
+    for (int32_t i = 0; i < p->nfields + p->nterms; i++) {
+        const bool term = i >= p->nfields;
+        const ngx_lookup_cond& q = term ? p->terms[i - p->nfields] : p->fields[i];
+        LookupCond& k = conds[i];
+        k = LookupCond{};
+        int32_t type;
+        if (int32_t rc = column(q.field, k.col, type)) return rc;
+        k.kind = lookupKindOf(type);
+        if (q.kind < NGX_LK_INT || q.kind > NGX_LK_STRING) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: unknown constant kind");
+        k.ckind = q.kind;
+        k.op = q.op;
+        if (term) {
+            if (q.op < kLkLT || q.op > kLkNE) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: unknown operator");
+            k.lo = static_cast<uint64_t>(q.kind == NGX_LK_BOOL ? (q.bits ? 1 : 0) : q.bits);
+        } else {
+            if (q.kind != k.kind) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: a scanned field's constant is not of the field's type");
+            k.lo = k.kind == kLkBool ? (q.bits ? 1 : 0) : q.lo;
+            k.hi = q.hi;
+        }
+        if (q.kind == NGX_LK_STRING) {
+            if (q.str_len >= (1ULL << 31) || (q.str_len && !q.str)) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: string constant");
+            k.soff = pool.size();
+            k.slen = static_cast<int32_t>(q.str_len);
+            pool.append(q.str ? q.str : "", q.str_len);
+        }
+        rowBytes += k.kind == kLkInt ? k.col.width : k.kind == kLkBool ? 1 : 8;
+    }
+    std::vector<LookupYield> ys(p->nyields);
+    static const int32_t keyTypeV[1] = {NGX_T_VID}, keyTypeE[3] = {NGX_T_VID, NGX_T_VID, NGX_T_INT};
+    R.colTypes.assign(edge ? keyTypeE : keyTypeV, (edge ? keyTypeE : keyTypeV) + nkey);
+    bool anyString = false;
+    for (int32_t y = 0; y < p->nyields; y++) {
+        int32_t type;
+        ys[y] = LookupYield{};
+        if (int32_t rc = column(p->yields[y], ys[y].col, type)) return rc;
+        ys[y].cell = type;                                        // NGX_CELL_* numbers its kinds as NGX_T_*
+        anyString |= type == NGX_T_STRING;
+        R.colTypes.push_back(type);
+    }
+    const int32_t ncols = nkey + p->nyields;
+    R.r.ncols = ncols;
+    R.r.col_types = R.colTypes.data();
+    HIP_OK(hipSetDevice(c->device));
+    uint64_t n = 0;
+    if (slot >= 0) n = edge ? (d.V ? readScalar(c, d.slots[slot].off + d.V) : 0) : d.V;
+    R.r.scanned_rows = n;
+    R.r.keep_bytes = n * rowBytes;
+    if (n == 0) {                                                 // no row of the tag / no edge of the type
+        c->lookupDevice++;
+        return NGX_OK;
+    }
+    for (hipEvent_t& e : c->gbEv)
+        if (!e) HIP_OK(hipEventCreate(&e));
+    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
+    HIP_OK(hipEventRecord(ev0, c->stream));
+    LookupArgs a{};
+    a.n = n;
+    a.V = d.V;
+    a.edge = edge ? 1 : 0;
+    a.nf = p->nfields;
+    a.nt = p->nterms;
+    a.ny = p->nyields;
+    a.vid = d.vid;
+    if (edge) a.slot = d.slots[slot];
+    else a.present = d.tags[slot].present;
+    LookupCond* condsDev = c->lkConds.get<LookupCond>(std::max<size_t>(conds.size(), 1));
+    if (!conds.empty()) HIP_OK(hipMemcpyAsync(condsDev, conds.data(), conds.size() * sizeof(LookupCond), hipMemcpyHostToDevice, c->stream));
+    char* poolDev = c->lkPool.get<char>(std::max<size_t>(pool.size(), 1));
+    if (!pool.empty()) HIP_OK(hipMemcpyAsync(poolDev, pool.data(), pool.size(), hipMemcpyHostToDevice, c->stream));
+    LookupYield* ysDev = c->lkYs.get<LookupYield>(std::max<size_t>(ys.size(), 1));
+    if (!ys.empty()) HIP_OK(hipMemcpyAsync(ysDev, ys.data(), ys.size() * sizeof(LookupYield), hipMemcpyHostToDevice, c->stream));
+    a.conds = condsDev;
+    a.pool = poolDev;
+    a.ys = ysDev;
+    const uint64_t chunks = (n + 255) / 256;
+    a.keep = c->lkKeep.get<uint8_t>(n);
+    a.chunkCount = c->lkCount.get<uint64_t>(chunks + 1);
+    uint64_t* base = c->lkBase.get<uint64_t>(chunks + 1);
+    uint64_t* tiles = c->lkTiles.get<uint64_t>((chunks + kTile - 1) / kTile + 1);
+    a.chunkBase = base;
+    a.gridMax = c->lookupGridMax;
+    HIP_OK(hipStreamSynchronize(c->stream));                      // the descriptors are pageable: copied before they go
+    c->timed("lookup_keep", n * rowBytes + n, [&] {
+        if (launchLookupKeep(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup keep"};
+    });
+    c->timed("lookup_scan", chunks * 16, [&] {
+        if (launchScanU64(a.chunkCount, chunks, base, tiles, c->stream)) throw Error{NGX_E_DEVICE, "lookup scan"};
+    });
+    const uint64_t m = readScalar(c, base + chunks);
+    if (m > n) throw Error{NGX_E_DEVICE, "lookup: inconsistent counts"};
+    if (m > static_cast<uint64_t>(c->lookupRowsMax))
+        return fail(c, NGX_E_UNSUPPORTED, "lookup: " + std::to_string(m) + " rows, above lookup_rows_max");
+    uint64_t strBytes = 0;
+    if (m) {
+        if (anyString) {
+            uint64_t* slen = c->lkSlen.get<uint64_t>(m + 1);
+            uint64_t* spre = c->lkSpre.get<uint64_t>(m + 1);
+            uint64_t* stiles = c->lkTiles.get<uint64_t>(std::max((m + kTile - 1) / kTile + 1, (chunks + kTile - 1) / kTile + 1));
+            a.lenOut = slen;
+            c->timed("lookup_emit", m * 8, [&] {
+                if (launchLookupEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup string lengths"};
+            });
+            c->timed("lookup_scan", m * 16, [&] {
+                if (launchScanU64(slen, m, spre, stiles, c->stream)) throw Error{NGX_E_DEVICE, "lookup string scan"};
+            });
+            strBytes = readScalar(c, spre + m);
+            a.lenOut = nullptr;
+            a.strPre = spre;
+            a.strOut = c->lkStr.get<char>(std::max<uint64_t>(strBytes, 1));
+        }
+        a.cells = c->lkCells.get<GroupCell>(m * ncols);
+        c->timed("lookup_emit", n + m * ncols * sizeof(GroupCell) + strBytes, [&] {
+            if (launchLookupEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup emit"};
+        });
+    }
+    HIP_OK(hipEventRecord(ev1, c->stream));
+    R.cells.resize(m * ncols);
+    if (m) HIP_OK(hipMemcpyAsync(R.cells.data(), a.cells, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
+    R.strings.resize(strBytes);
+    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], a.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+    c->collectTimings();
+    R.r.device_ms = ms;
+    R.r.nrows = m;
+    R.r.cells = R.cells.data();
+    R.r.strings = R.strings.data();
+    R.r.strings_len = strBytes;
+    c->lookupDevice++;
+    return NGX_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t ngx_lookup(ngx_ctx* c, const ngx_lookup_plan* plan, ngx_lookup_result** out) {
+    if (!c || !plan || !out) return NGX_E_BAD_ARGUMENT;
+    std::lock_guard<std::mutex> g(c->mu);
+    auto R = std::make_unique<LookupResultHolder>();
+    int32_t rc;
+    try {
+        rc = lookupOp(c, plan, *R);
+    } catch (const Error& e) {
+        rc = fail(c, e.code, e.msg);
+    }
+    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
+    R->r.code = rc;
+    *out = &R.release()->r;
+    return rc;
+}
+
+extern "C" void ngx_lookup_result_free(ngx_lookup_result* r) {
+    if (r) delete reinterpret_cast<LookupResultHolder*>(r);
 }
 
 // ------------------------------------------------------------------------ FIND SHORTEST PATH (ngx_find_path)

@@ -710,6 +710,58 @@ struct FetchArgs {
 int launchFetchKeys(const FetchArgs& a, hipStream_t s);
 int launchFetchEmit(const FetchArgs& a, hipStream_t s);
 
+// LOOKUP ON a tag / an edge type as a column scan in HBM (lookup.hip; ngx_lookup). Three steps, every one a sweep
+// of 256 rows a workgroup and turn, so rows keep storage order under every grid size:
+//   keep   a thread per row of the tag table (present[row] set) or per edge of the type's out-slot: the scanned
+//          fields encoded to their index key and compared with [lo, hi) (lo == hi: equality, the reference's prefix
+//          scan), BOOL / STRING fields compared typed, then the residual terms. keep[row] and the kept rows of each
+//          256-row chunk (ballot / popcount) are written.
+//   scan   launchScanU64 over the chunk counts: exclusive bases; the total sizes the output exactly.
+//   emit   VertexID | SrcVID, DstVID, Ranking and the YIELD columns of the kept rows at base[chunk] + rank in chunk;
+//          an edge's source row is the last row with off[row] <= e. Run twice when a yield is a string (lengths,
+//          then cells), as FETCH's emit.
+constexpr int kLookupMax = 16;                      // scanned fields, residual terms, YIELD columns: each at most
+constexpr uint32_t kLookupGridMax = 2048;
+enum { kLkInt = 0, kLkDouble, kLkBool, kLkString };                 // how a column is stored / what a constant is
+enum { kLkLT = 0, kLkLE, kLkGT, kLkGE, kLkEQ, kLkNE };              // RelationalExpression::Operator
+struct LookupCond {
+    DCol col;
+    int32_t kind;                       // kLk* of the column
+    int32_t ckind;                      // term: kLk* of the constant
+    int32_t op;                         // term: kLk?? operator (column op constant)
+    int32_t slen;                       // string constant: its length
+    uint64_t lo, hi;                    // scanned INT / DOUBLE field: key range; BOOL field: lo = the constant;
+                                        // term: lo = the constant's bits (int64 / double / 0, 1)
+    uint64_t soff;                      // string constant: its offset in pool
+};
+struct LookupYield {
+    DCol col;
+    int32_t cell;                       // NGX_CELL_* of the output cell
+    int32_t pad;
+};
+struct LookupArgs {
+    uint64_t n;                         // rows scanned: V (tag) or the slot's edges
+    uint64_t V;
+    int32_t edge;
+    int32_t nf, nt, ny;
+    const uint8_t* present;             // tag: DTag::present
+    const int64_t* vid;                 // the vertex table's vids
+    DSlot slot;                         // edge: the type's out-slot
+    const LookupCond* conds;            // device array: nf scanned fields, then nt residual terms
+    const char* pool;                   // string constants
+    const LookupYield* ys;              // device array
+    uint8_t* keep;                      // per row
+    uint64_t* chunkCount;               // per 256-row chunk: kept rows
+    const uint64_t* chunkBase;          // exclusive scan of chunkCount (emit)
+    uint64_t* lenOut;                   // emit, length pass: per output row its string bytes; null: the cell pass
+    const uint64_t* strPre;             // cell pass: exclusive scan of the lengths; null: no string yields
+    char* strOut;
+    GroupCell* cells;                   // m * (nkey + ny): nkey = 1 (VertexID) or 3 (SrcVID, DstVID, Ranking)
+    uint32_t gridMax;                   // most workgroups of a sweep (flag lookup_grid_max); 0: kLookupGridMax
+};
+int launchLookupKeep(const LookupArgs& a, hipStream_t s);
+int launchLookupEmit(const LookupArgs& a, hipStream_t s);
+
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

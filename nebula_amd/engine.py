@@ -274,6 +274,37 @@ class FetchSpec:
     prefix: List[str] = field(default_factory=list)               # the names when nothing comes back
 
 
+class LookupCondC(ctypes.Structure):
+    _fields_ = [("field", ctypes.c_char_p), ("kind", c_i32), ("op", c_i32), ("lo", c_u64), ("hi", c_u64),
+                ("bits", c_i64), ("str", ctypes.c_char_p), ("str_len", c_u64)]
+
+
+class LookupPlanC(ctypes.Structure):
+    _fields_ = [("space", c_i32), ("is_edge", c_i32), ("schema_id", c_i32), ("nfields", c_i32),
+                ("fields", P(LookupCondC)), ("nterms", c_i32), ("terms", P(LookupCondC)), ("nyields", c_i32),
+                ("yields", P(ctypes.c_char_p))]
+
+
+class LookupResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("nrows", c_u64), ("cells", P(Cell)),
+                ("strings", ctypes.c_void_p), ("strings_len", c_u64), ("scanned_rows", c_u64), ("keep_bytes", c_u64),
+                ("device_ms", c_dbl)]
+
+
+@dataclass
+class LookupSpec:
+    """ngx_lookup_plan of a planned LOOKUP sentence (lookup.device_spec builds it from a lookup.Plan), and the names
+    and schema types lookup.device_rows gives the rows.
+    fields / terms: (field, NGX_LK_* of the constant, operator, lo, hi, bits, string bytes)."""
+    is_edge: bool
+    schema_id: int
+    fields: List[Tuple[str, int, int, int, int, int, bytes]]
+    terms: List[Tuple[str, int, int, int, int, int, bytes]]
+    yields: List[str]
+    names: List[str]
+    types: List[int]
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -315,6 +346,8 @@ SIGNATURES = {
     "ngx_fetch": (c_i32, [ctypes.c_void_p, P(GoResultC), P(FetchPlanC), P(P(FetchResultC))]),
     "ngx_go_fetch": (c_i32, [ctypes.c_void_p, P(GoPlan), P(FetchPlanC), P(P(FetchResultC))]),
     "ngx_fetch_result_free": (None, [P(FetchResultC)]),
+    "ngx_lookup": (c_i32, [ctypes.c_void_p, P(LookupPlanC), P(P(LookupResultC))]),
+    "ngx_lookup_result_free": (None, [P(LookupResultC)]),
     "ngx_find_path": (c_i32, [ctypes.c_void_p, P(PathPlanC), P(P(PathResultC))]),
     "ngx_path_result_free": (None, [P(PathResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
@@ -449,6 +482,7 @@ class GoResult:
     ngroups: int = 0                     # group_by + order_by: the groups the window was cut from
     path_found: int = 0                  # find_path: bit j set when target j was found (ngx_path_result.found)
     tags_seen: int = 0                   # fetch: bit t set when some key had a row of the plan's tag t
+    keep_bytes: int = 0                  # lookup: bytes the keep pass had to read
 
 
 @dataclass
@@ -493,6 +527,7 @@ class Engine:
     device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
     device_find_path = True                    # find_path(space, sentence) searches FIND SHORTEST PATH in HBM
     device_fetch = True                        # fetch(space, spec) / go_fetch(space, go, spec) look keys up and gather in HBM
+    device_lookup = True                       # lookup(space, spec) scans a tag's / an edge type's columns in HBM
 
     def __init__(self, device: int = 0, rank: int = 0, world: int = 1, nccl_id: Optional[bytes] = None,
                  exchange=None):
@@ -943,6 +978,37 @@ class Engine:
             return self._fetch_result(rc, out, rows)
         finally:
             self.L.ngx_fetch_result_free(out)
+
+    def lookup(self, space: int, spec: LookupSpec, rows: bool = True) -> GoResult:
+        """LOOKUP ON a tag / an edge type as one streaming pass over its columns in HBM (ngx_lookup). GoResult.rows /
+        nrows / col_types are the output's (VertexID | SrcVID, DstVID, Ranking, then the yields, in storage order),
+        go_nrows the rows scanned, device_ms the call's. NGX_E_UNSUPPORTED ("lookup: ...") and plan errors come back
+        as a result with the code and text: no host path stands behind a refusal."""
+        def conds(items):
+            arr = (LookupCondC * max(1, len(items)))()
+            for i, (fld, kind, op, lo, hi, bits, sb) in enumerate(items):
+                arr[i].field, arr[i].kind, arr[i].op, arr[i].lo, arr[i].hi = fld.encode(), kind, op, lo, hi
+                arr[i].bits, arr[i].str, arr[i].str_len = bits, sb, len(sb)
+            return arr
+        fields, terms = conds(spec.fields), conds(spec.terms)
+        ys = (ctypes.c_char_p * max(1, len(spec.yields)))(*[y.encode() for y in spec.yields])
+        plan = LookupPlanC(space, 1 if spec.is_edge else 0, spec.schema_id, len(spec.fields), fields, len(spec.terms),
+                           terms, len(spec.yields), ys)
+        out = P(LookupResultC)()
+        rc = self.L.ngx_lookup(self.h, ctypes.byref(plan), ctypes.byref(out))
+        try:
+            err = self.L.ngx_last_error(self.h).decode() if rc else ""
+            if rc == E_DEVICE:
+                raise EngineError(rc, err)
+            o = out.contents
+            res = GoResult(ok=rc == 0, error=err, code=rc, col_types=o.col_types[:o.ncols] if o.ncols else [], rows=[],
+                           nrows=o.nrows, device_ms=o.device_ms, go_nrows=o.scanned_rows, keep_bytes=o.keep_bytes)
+            if rc == 0 and rows:
+                strings = ctypes.string_at(o.strings, o.strings_len) if o.strings_len else b""
+                res.rows = _cells(o.cells, o.nrows, o.ncols, strings)
+            return res
+        finally:
+            self.L.ngx_lookup_result_free(out)
 
     def find_path(self, space: int, s: Union[str, ngql.FindPathSentence], from_vids: Optional[Sequence[int]] = None,
                   to_vids: Optional[Sequence[int]] = None, rows: bool = True) -> GoResult:

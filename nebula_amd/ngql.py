@@ -1021,3 +1021,42 @@ def parse_fetch(src: str):
             raise SyntaxError("syntax error near `YIELD'")
     p.expect("eof")
     return s
+
+
+# ----------------------------------------------------------------------------- LOOKUP sentence
+# lookup_sentence (parser.yy): LOOKUP ON <name> lookup_where_clause [yield_clause]. LOOKUP is matched as a word
+# (_word), so every other text lexes as before. The WHERE of a LOOKUP has no bare column names: `WHERE col1 == 200`
+# is the reference's syntax error (a name stands only before `.` or `(`).
+@dataclass
+class LookupSentence:
+    from_: str = ""
+    where: Optional[Expr] = None                                  # None: no WHERE ("Where clause is required")
+    has_yield: bool = False
+    yields: List[AggCol] = field(default_factory=list)
+
+
+def is_lookup(src: str) -> bool:
+    return re.match(r"\s*LOOKUP\b", src, re.I) is not None
+
+
+def parse_lookup(src: str) -> LookupSentence:
+    p = Parser(src)
+    for word in ("LOOKUP", "ON"):
+        if _word(p, word) is None:
+            raise SyntaxError(f"expected {word}, got {p.peek().text!r}")
+    s = LookupSentence(from_=p.label())
+    if p.accept("kw", "WHERE"):
+        start = p.i
+        s.where = p.expression()
+        for j in range(start, p.i):
+            t, nxt, prev = p.toks[j], p.toks[j + 1], p.toks[j - 1]
+            if t.kind == "name" and not (nxt.kind == "op" and nxt.text in (".", "(")) \
+                    and not (prev.kind == "op" and prev.text == "."):
+                raise SyntaxError(f"syntax error near `{t.text}'")
+    if p.accept("kw", "YIELD"):
+        s.has_yield = True
+        s.yields = _agg_columns(p)
+        if not s.yields:
+            raise SyntaxError("syntax error near `YIELD'")
+    p.expect("eof")
+    return s

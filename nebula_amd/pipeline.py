@@ -30,6 +30,12 @@ library, include/nebula_gn.h ngx_go with input_* set):
     (nebula_amd/fetch.py), when the caller opts in with fetch=True and hands the space's schemas (catalog=). It
     calls onResult_: its rows feed the sentence piped behind it. The key lookup and the property gather run in one
     device call where the backend has it (ngx_fetch; behind a plain head GO, ngx_go_fetch; Pipeline._fetch).
+  - LookupExecutor (src/graph/LookupExecutor.cpp): `LOOKUP ON <tag|edge> WHERE ... [YIELD ...]`
+    (nebula_amd/lookup.py), when the caller opts in with lookup=True and hands the space's indexes
+    (indexes=[lookup.Index, ...]). feedResult keeps its input unused: `GO ... | LOOKUP ...` ignores the input. It
+    calls onResult_: its rows (VertexID | SrcVID, DstVID, Ranking, then the yields) feed the sentence piped behind
+    it. The scan is the backend's (Engine.lookup, ngx_lookup): no host storage leg stands behind it, so a
+    "lookup: ..." refusal is the sentence's error.
 GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
 default keeps refusing them, as `| YIELD` is refused either way).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
@@ -41,6 +47,7 @@ from typing import Dict, List, Optional, Sequence
 
 from . import fetch as fetchmod
 from . import findpath, groupby, ngql, orderby, setop
+from . import lookup as lookupmod
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
 _KIND_TYPE = {"bool": T_BOOL, "int": T_INT, "id": T_INT, "timestamp": T_INT, "float": T_DOUBLE,
@@ -161,8 +168,13 @@ class Pipeline:
     def __init__(self, backend, space: int, edge_names: Sequence[str] = (), device_group_by: bool = True,
                  order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
                  set_ops: bool = False, device_set_op: bool = True, find_path: bool = False,
-                 device_find_path: bool = True, fetch: bool = False, device_fetch: bool = True, catalog=None, **go_kw):
-        """fetch=True: FETCH PROP ON sentences run (off by default, as the other opt-ins are); catalog is the
+                 device_find_path: bool = True, fetch: bool = False, device_fetch: bool = True, catalog=None,
+                 lookup: bool = False, indexes=None, **go_kw):
+        """lookup=True: LOOKUP ON sentences run (off by default, as the other opt-ins are); indexes are the space's
+        lookup.Index items (what the meta client's index cache holds); the schemas come from catalog, as for fetch.
+        The backend has to have `lookup` (an Engine): the oracle has no index scan, and the Pipeline refuses to be
+        built over it with lookup=True. lookups counts the sentences scanned, lookup_rows their rows.
+        fetch=True: FETCH PROP ON sentences run (off by default, as the other opt-ins are); catalog is the
         space's fetch.Catalog (partition count, tag and edge schemas: what the executors ask the schema manager);
         an Engine backend hands its own (Engine.catalog), the oracle backend needs it passed.
         device_fetch=False: every FETCH takes the host restatement (fetch.py) even where the backend could look the
@@ -190,8 +202,16 @@ class Pipeline:
         self.find_path_refusal = ""                               # the last refusal's text
         self.fetch = fetch
         self.device_fetch = device_fetch
-        if catalog is None and fetch and hasattr(backend, "catalog"):
+        self.lookup = lookup
+        self.indexes = list(indexes or [])
+        self.lookups = 0
+        self.lookup_rows = 0
+        if lookup and not hasattr(backend, "lookup"):
+            raise PipelineError("lookup=True needs a backend with lookup(space, spec): an Engine")
+        if catalog is None and (fetch or lookup) and hasattr(backend, "catalog"):
             catalog = backend.catalog(space)                      # an Engine knows the schemas it was given
+        if lookup and catalog is None:
+            raise PipelineError("lookup=True needs the space's schemas: catalog=fetch.Catalog(...)")
         if fetch and catalog is None:
             raise PipelineError("fetch=True needs the space's schemas: catalog=fetch.Catalog(...)")
         self.catalog = catalog
@@ -618,6 +638,26 @@ class Pipeline:
             return None
         return s if plain_go(s) else None
 
+    def _lookup(self, text: str) -> Outcome:
+        """A LOOKUP sentence: graphd's checks and the index choice, storaged's scan policy (lookup.plan_of), then the
+        backend's scan. The input of the pipe is not read (LookupExecutor::feedResult keeps it unused)."""
+        try:
+            s = ngql.parse_lookup(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        try:
+            plan = lookupmod.plan_of(self.catalog, self.indexes, s)
+        except lookupmod.LookupError as e:
+            return Outcome(False, str(e))
+        spec = lookupmod.device_spec(plan)
+        r = self.backend.lookup(self.space, spec)
+        if not r.ok:
+            return Outcome(False, r.error, list(plan.names))
+        self.lookups += 1
+        self.lookup_rows += r.nrows
+        names, types, rows = lookupmod.device_rows(spec, r)
+        return Outcome(True, "", names, types, rows)
+
     def _operand(self, text: str) -> Outcome:
         """One operand of a set sentence: a piped sentence, or a parenthesised set sentence."""
         body = _unwrap(text)
@@ -647,6 +687,14 @@ class Pipeline:
                 if len(_split(body, "|")) == 1 and ngql.is_fetch(body):
                     try:
                         ngql.parse_fetch(body)
+                    except (SyntaxError, ValueError) as e:
+                        return Outcome(False, "SyntaxError: %s" % e)
+        if self.lookup:
+            for part in parts:
+                body = _unwrap(part)
+                if len(_split(body, "|")) == 1 and ngql.is_lookup(body):
+                    try:
+                        ngql.parse_lookup(body)
                     except (SyntaxError, ValueError) as e:
                         return Outcome(False, "SyntaxError: %s" % e)
         cur = inp
@@ -719,6 +767,8 @@ class Pipeline:
                 out = self._limit(body, cur)
             elif self.fetch and ngql.is_fetch(body):
                 out = self._fetch(body, cur)
+            elif self.lookup and ngql.is_lookup(body):
+                out = self._lookup(body)
             elif self.find_path and ngql.is_find_path(body):
                 out = self._find_path(body, cur)
                 if not out.ok:
@@ -757,8 +807,9 @@ class Pipeline:
 def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_group_by: bool = True,
         order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
         set_ops: bool = False, device_set_op: bool = True, find_path: bool = False, device_find_path: bool = True,
-        fetch: bool = False, device_fetch: bool = True, catalog=None, **go_kw) -> Outcome:
+        fetch: bool = False, device_fetch: bool = True, catalog=None, lookup: bool = False, indexes=None,
+        **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
                     device_order_by=device_order_by, device_group_order=device_group_order, set_ops=set_ops,
                     device_set_op=device_set_op, find_path=find_path, device_find_path=device_find_path, fetch=fetch,
-                    device_fetch=device_fetch, catalog=catalog, **go_kw).run(text)
+                    device_fetch=device_fetch, catalog=catalog, lookup=lookup, indexes=indexes, **go_kw).run(text)
