@@ -3465,8 +3465,11 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
     // whether the shards hold that per-hop all-gather, from values every shard has alike (the query,
     // the world), so all of them enter it; what a shard itself can do (its rows, limits, flags) travels
     // inside it
-    const bool pullGather = c->world > 1 && !rw && hs.n >= 1 && hs.n <= kPullMaxSlots && d.vglobal < (1ULL << 31) &&
-                            c->world <= kMaxWorld;
+    // (the OVER types of the query, not hs.n: a shard that holds no row of a type has no slot for it, and with
+    // hs.n it stayed out of the all-gather its peers entered: a collective mismatch)
+    const size_t overSlots = gp.edgeTypes.size();
+    const bool pullGather = c->world > 1 && !rw && overSlots >= 1 && overSlots <= static_cast<size_t>(kPullMaxSlots) &&
+                            d.vglobal < (1ULL << 31) && c->world <= kMaxWorld;
     bool pullable = !rw && c->pullFactor > 0 && (c->world == 1 || (d.vglobal < (1ULL << 31) && c->world <= kMaxWorld)) &&
                     hs.n >= 1 && hs.n <= kPullMaxSlots && d.V < (1ULL << 32) && d.mirror.size() == d.slots.size();
     if (pullable) {
@@ -3474,7 +3477,9 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
         pa.n = hs.n;
         for (int s = 0; s < hs.n && pullable; s++) {
             const int32_t m = d.mirror[hs.slotIdx[s]];
-            if (m < 0 || d.pullHead.size() != d.slots.size() || !d.pullHead[hs.slotIdx[s]].perm) { pullable = false; break; }
+            // (a shard without rows has an empty head image, perm == nullptr: it can pull, launchPull has nothing to do;
+            // counted as unable it kept every shard of the world from pulling)
+            if (m < 0 || d.pullHead.size() != d.slots.size() || (!d.pullHead[hs.slotIdx[s]].perm && d.V > 0)) { pullable = false; break; }
             const DeviceGraph::PullHead& ph = d.pullHead[hs.slotIdx[s]];
             pa.ioff[s] = d.slots[m].off;
             pa.isrc[s] = d.slots[m].dgid;
@@ -4222,7 +4227,7 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
             // 4 B each, against (peer rows) / 8 B per peer. Every shard decides alike (the gathered E).
             uint64_t minPeer = ~0ULL;
             for (int q = 0; q < c->world; q++) minPeer = std::min<uint64_t>(minPeer, d.shardBase[q + 1] - d.shardBase[q]);
-            const bool lists = c->xchgLists > 0 || (c->xchgLists < 0 && eMaxKnown && 32 * eMaxShard < minPeer);
+            const bool lists = c->xchgLists > 0 || (c->xchgLists < 0 && eMaxKnown && kXchgListFactor * eMaxShard < minPeer);
             c->timed("exchange", 0, [&] {
                 if (lists) exchangeFrontierList(c, d, ep);
                 else exchangeFrontier(c, d, ep);

@@ -777,6 +777,7 @@ int launchCopyBatch(const CopyBatch& b, hipStream_t s);
 int launchVertexCells(const VertexCellArgs& a, hipStream_t s);
 // frontier exchange, one launch each side: pack every peer q's marked rows into bits + q * words;
 // merge ORs the world - 1 received bitmaps (bits + q * words, over this shard's rows) into the marks
+constexpr int kXchgBlock = 256;                      // k_pack / k_merge: rows per workgroup (four ballot words)
 struct ExchangeArgs {
     uint8_t* visited;
     uint8_t epoch;
@@ -791,6 +792,9 @@ int launchMergePeers(const ExchangeArgs& a, hipStream_t s);
 // (counts, then the vids): per peer q != rank the marked rows of q's range as u32 offsets
 // from sb[q], appended to list[q * cap ..] (one atomic per workgroup and peer; counts[q] zeroed by the
 // host first), then each owner marks the rows it received (k_merge_list).
+constexpr int kListThreads = 1024;                   // k_pack_list: threads per workgroup
+constexpr int kListTile = 4096;                      // k_pack_list: rows per workgroup (kListThreads x 4)
+constexpr int kXchgListFactor = 32;                  // lists when kXchgListFactor * (largest shard's E) < smallest shard's rows
 struct ListXchgArgs {
     const uint8_t* visited;
     uint8_t epoch;

@@ -1442,7 +1442,7 @@ struct WriteArr {
 // pack this shard's marks for peer q's rows into a bitmap: one row byte per lane (coalesced), the
 // wave's ballot is the 64-bit word of its 64 rows; merge received bitmaps into visited
 // grid.y = peer; a wave's ballot is one bitmap word (the whole block leaves together for q == rank)
-__global__ __launch_bounds__(256) void k_pack(const ExchangeArgs a) {
+__global__ __launch_bounds__(kXchgBlock) void k_pack(const ExchangeArgs a) {
     const int q = blockIdx.y;
     if (q == a.rank) return;
     const uint64_t lo = a.sb[q], n = a.sb[q + 1] - lo;
@@ -1452,7 +1452,7 @@ __global__ __launch_bounds__(256) void k_pack(const ExchangeArgs a) {
     if ((threadIdx.x & 63) == 0 && i < n) a.bits[q * a.words + (i >> 6)] = word;
 }
 // one thread per own row: the OR over the peers' words (each a wave-wide broadcast load), one store
-__global__ __launch_bounds__(256) void k_merge(const ExchangeArgs a) {
+__global__ __launch_bounds__(kXchgBlock) void k_merge(const ExchangeArgs a) {
     const uint64_t lo = a.sb[a.rank], n = a.sb[a.rank + 1] - lo;
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1814,21 +1814,22 @@ int launchVertexCells(const VertexCellArgs& a, hipStream_t s) {
     return static_cast<int>(hipGetLastError());
 }
 
-// list pack: 1024 threads x 4 rows per workgroup (row = tile + k * 1024 + thread: coalesced mark loads),
-// blockIdx.y = peer
-__global__ __launch_bounds__(1024) void k_pack_list(ListXchgArgs a) {
-    __shared__ uint64_t sm[1024 / 64 + 1];
+// list pack: kListThreads threads x 4 rows per workgroup (row = tile + k * kListThreads + thread: coalesced
+// mark loads), blockIdx.y = peer
+static_assert(kListTile == 4 * kListThreads && kListThreads == 1024, "k_pack_list: 16 waves, four rows per thread");
+__global__ __launch_bounds__(kListThreads) void k_pack_list(ListXchgArgs a) {
+    __shared__ uint64_t sm[kListThreads / 64 + 1];
     __shared__ uint64_t sBase;
     const int q = blockIdx.y;
     if (q == a.rank && !a.includeSelf) return;
     const uint64_t n = a.sb[q + 1] - a.sb[q];
-    const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * 4096;
+    const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kListTile;
     if (tile >= n) return;
     const uint8_t* mk = a.visited + a.sb[q];
     uint32_t flags = 0;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const uint64_t r = tile + k * 1024 + threadIdx.x;
+        const uint64_t r = tile + k * kListThreads + threadIdx.x;
         const uint8_t m = mk[r < n ? r : n - 1];
         flags |= (r < n && m == a.epoch ? 1u : 0u) << k;
     }
@@ -1854,7 +1855,7 @@ __global__ __launch_bounds__(1024) void k_pack_list(ListXchgArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         if (!((flags >> k) & 1u)) continue;
-        if (at < a.cap) out[at] = static_cast<uint32_t>(tile + k * 1024 + threadIdx.x);
+        if (at < a.cap) out[at] = static_cast<uint32_t>(tile + k * kListThreads + threadIdx.x);
         at++;
     }
 }
@@ -1880,7 +1881,8 @@ int launchPackLists(const ListXchgArgs& a, hipStream_t s) {
     for (int q = 0; q < a.world; q++)
         if (q != a.rank || a.includeSelf) maxRows = std::max(maxRows, a.sb[q + 1] - a.sb[q]);
     if (maxRows == 0 || a.world < 2 || a.world > kMaxWorld) return 0;
-    hipLaunchKernelGGL(k_pack_list, dim3(static_cast<unsigned>((maxRows + 4095) / 4096), a.world), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_pack_list, dim3(static_cast<unsigned>((maxRows + kListTile - 1) / kListTile), a.world),
+                       dim3(kListThreads), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 
@@ -1895,14 +1897,14 @@ int launchPackPeers(const ExchangeArgs& a, hipStream_t s) {
     for (int q = 0; q < a.world; q++)
         if (q != a.rank) maxRows = std::max(maxRows, a.sb[q + 1] - a.sb[q]);
     if (maxRows == 0 || a.world < 2 || a.world > kMaxWorld) return 0;
-    hipLaunchKernelGGL(k_pack, dim3(static_cast<unsigned>((maxRows + 255) / 256), a.world), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_pack, dim3(static_cast<unsigned>((maxRows + kXchgBlock - 1) / kXchgBlock), a.world), dim3(kXchgBlock), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 
 int launchMergePeers(const ExchangeArgs& a, hipStream_t s) {
     const uint64_t n = a.sb[a.rank + 1] - a.sb[a.rank];
     if (n == 0 || a.world < 2 || a.world > kMaxWorld) return 0;
-    hipLaunchKernelGGL(k_merge, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_merge, dim3(static_cast<unsigned>((n + kXchgBlock - 1) / kXchgBlock)), dim3(kXchgBlock), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 

@@ -53,9 +53,16 @@ K_PULL_MAX_SLOTS = 4            # kernels.h   kPullMaxSlots
 K_COMPACT_TILE = 4096           # kernels.h   kCompactTile
 K_RESV_SHIFT = 16               # kargs.h     kResvShift
 K_RESV_GROUPS = 8               # kargs.h     kResvGroups
+K_XCHG_BLOCK = 256              # kernels.h   kXchgBlock (k_pack / k_merge rows per workgroup)
+K_LIST_THREADS = 1024           # kernels.h   kListThreads (k_pack_list)
+K_LIST_TILE = 4096              # kernels.h   kListTile (k_pack_list rows per workgroup)
+K_XCHG_LIST_FACTOR = 32         # kernels.h   kXchgListFactor (lists iff 32 * E of the busiest shard < smallest shard)
+K_MAX_WORLD = 64                # kernels.h   kMaxWorld
 CONSTANTS = {
     "kernels.h": {"kSeedFuseMax": K_SEED_FUSE_MAX, "kPullK": K_PULL_K, "kPullWindow": K_PULL_WINDOW,
-                  "kPullSeg": K_PULL_SEG, "kPullMaxSlots": K_PULL_MAX_SLOTS, "kCompactTile": K_COMPACT_TILE},
+                  "kPullSeg": K_PULL_SEG, "kPullMaxSlots": K_PULL_MAX_SLOTS, "kCompactTile": K_COMPACT_TILE,
+                  "kXchgBlock": K_XCHG_BLOCK, "kListThreads": K_LIST_THREADS, "kListTile": K_LIST_TILE,
+                  "kXchgListFactor": K_XCHG_LIST_FACTOR, "kMaxWorld": K_MAX_WORLD},
     "kargs.h": {"kChunk": K_CHUNK, "kResvShift": K_RESV_SHIFT, "kResvGroups": K_RESV_GROUPS},
     "final_kernels.h": {"WG": K_WG},
 }
@@ -270,17 +277,55 @@ def new_space():
     return _space[0]
 
 
-def csr_slots(graph):
+def part_of(vid, num_parts):
+    """ID_HASH: the part of a vid (the vid as an unsigned 64-bit number)."""
+    return (vid & (1 << 64) - 1) % num_parts + 1
+
+
+def shard_of(vid, num_parts, world):
+    """The engine's placement: part = vid mod num_parts + 1, shard = part % world."""
+    return part_of(vid, num_parts) % world
+
+
+def shard_tables(graph, num_parts, world, vids=None):
+    """(tables, shardBase): each shard's vertex list ordered by (part, vid), and the global row of each shard's first
+    row (world + 1 entries; global rows are the tables concatenated in rank order). vids: the vertices that have a row
+    (default: all of graph.vids, as ngx_load_csr is given them)."""
+    tables = [[] for _ in range(world)]
+    for v in sorted(graph.vids if vids is None else vids, key=lambda v: (part_of(v, num_parts), v)):
+        tables[shard_of(v, num_parts, world)].append(v)
+    base = [0]
+    for t in tables:
+        base.append(base[-1] + len(t))
+    return tables, base
+
+
+def kv_vertices(graph):
+    """The vertices a KV load knows: those with an out row, an in row or a tag row."""
+    have = set(graph.tags or {})
+    for a, b, _, _, _ in graph.edges:
+        have.add(a)
+        have.add(b)
+    return sorted(have)
+
+
+def csr_slots(graph, rank=None, world=1, num_parts=1):
     """ngx_load_csr's arrays of a Graph: (vpart, vid, slots), a slot pair (+t, -t) per type of graph.types, the rows'
-    edges in key order (rank, then dst, by their little-endian bytes)."""
-    row = {v: i for i, v in enumerate(graph.vids)}
-    nv = len(graph.vids)
+    edges in key order (rank, then dst, by their little-endian bytes). With a rank: that shard's rows only (the out slot
+    their out-edges, the in slot their in-edges; dst holds vids of any shard) and their parts."""
+    if rank is None:
+        vids, vpart = graph.vids, np.ones(len(graph.vids), np.int32)
+    else:
+        vids = shard_tables(graph, num_parts, world)[0][rank]
+        vpart = np.array([part_of(v, num_parts) for v in vids], np.int32)
+    row = {v: i for i, v in enumerate(vids)}
+    nv = len(vids)
     slots = []
     for t in graph.types:
         for sign in (1, -1):
             lists = [[] for _ in range(nv)]
             for a, b, tt, r, p in graph.edges:
-                if tt == t:
+                if tt == t and (a if sign > 0 else b) in row:
                     lists[row[a] if sign > 0 else row[b]].append((r, b if sign > 0 else a, p))
             off, dst, rank, cols = [0], [], [], ([], [], [])
             for lst in lists:
@@ -292,13 +337,13 @@ def csr_slots(graph):
                 off.append(len(dst))
             slots.append((sign * t, np.array(off, np.uint64), np.array(dst, np.int64), [np.array(c, np.int64) for c in cols],
                           np.array(rank, np.int64)))
-    return np.ones(nv, np.int32), np.array(graph.vids, np.int64), slots
+    return vpart, np.array(vids, np.int64), slots
 
 
-def load_engine_csr(e, graph, space=None, arrays=None):
+def load_engine_csr(e, graph, space=None, arrays=None, num_parts=1):
     """The graph through ngx_load_csr (exact layout, exact mirrors, one part, no tag rows). Returns the space."""
     space = space or new_space()
-    e.add_space(space, 1)
+    e.add_space(space, num_parts)
     for s in SCHEMA:
         e.add_schema(space, s.is_edge, s.sid, s.name, s.fields)
     e.load_csr(space, *(arrays or csr_slots(graph)))
@@ -306,31 +351,33 @@ def load_engine_csr(e, graph, space=None, arrays=None):
     return space
 
 
-def kv_batch(graph):
+def kv_batch(graph, num_parts=1):
+    """Every row of the graph, each key with the part of the vertex it is stored under (ngx_load_kv keeps the rows of
+    its shard's parts)."""
     b = kvfmt.KVBatch()
     types = [t for _, t in EDGE_FIELDS]
     for a, d, t, r, p in graph.edges:
         row = kvfmt.encode_row(types, list(p))
-        b.put(kvfmt.edge_key(1, a, t, r, d), row)
-        b.put(kvfmt.edge_key(1, d, -t, r, a), row)
+        b.put(kvfmt.edge_key(part_of(a, num_parts), a, t, r, d), row)
+        b.put(kvfmt.edge_key(part_of(d, num_parts), d, -t, r, a), row)
     for v, x in sorted((graph.tags or {}).items()):
-        b.put(kvfmt.vertex_key(1, v, TAG_ID), kvfmt.encode_row([kvfmt.INT], [x]))
+        b.put(kvfmt.vertex_key(part_of(v, num_parts), v, TAG_ID), kvfmt.encode_row([kvfmt.INT], [x]))
     return b
 
 
-def dataset(graph, space=None):
-    return fixtures.Dataset(space or new_space(), 1, SCHEMA, kv_batch(graph))
+def dataset(graph, space=None, num_parts=1):
+    return fixtures.Dataset(space or new_space(), num_parts, SCHEMA, kv_batch(graph, num_parts))
 
 
-def load_engine_kv(e, graph, space=None):
+def load_engine_kv(e, graph, space=None, num_parts=1):
     """The graph as KV rows (out and in row per edge, a tag row per entry of graph.tags). Returns the space."""
-    ds = dataset(graph, space)
+    ds = dataset(graph, space, num_parts)
     ds.load_engine(e)
     return ds.space
 
 
-def load_oracle(o, graph, space=None):
-    ds = dataset(graph, space)
+def load_oracle(o, graph, space=None, num_parts=1):
+    ds = dataset(graph, space, num_parts)
     ds.load_oracle(o)
     return ds.space
 
@@ -846,3 +893,416 @@ def _tag_case():
 case("tags", _tag_case, [Q("tags", n=2), Q("tags", m=1, n=2)], kv=True)
 
 RESV_ROWS = ((1 << K_RESV_SHIFT) - 1, 1 << K_RESV_SHIFT, (1 << K_RESV_SHIFT) + 1, K_RESV_GROUPS * (1 << K_RESV_SHIFT) + 1)
+
+
+# ----------------------------------------------------------------------------- shaped shards (world > 1)
+# Shared by tests/goshard_worker.py (one child process per rank rebuilds a case by name), tests/test_gpu_go_shards.py
+# and tests/test_goshard_host.py. num_parts = world, so a residue class of vid is one part on one shard and a shard's
+# rows are its vids in ascending order.
+class Shards:
+    """Vids such that shard q holds exactly counts[q] rows: local row i of shard q is `vid(q, i)`, global row
+    `row(q, i)`."""
+
+    def __init__(self, counts):
+        self.world = self.num_parts = len(counts)
+        self.counts = list(counts)
+        assert 2 <= self.world <= K_MAX_WORLD
+        self.base = [0]
+        for n in counts:
+            self.base.append(self.base[-1] + n)
+        self.vglobal = self.base[-1]
+
+    def vid(self, q, i):
+        assert 0 <= i < self.counts[q], (q, i)
+        return self.world * (i + 1) + (q - 1) % self.world
+
+    def row(self, q, i):
+        assert 0 <= i < self.counts[q], (q, i)
+        return self.base[q] + i
+
+    def vids(self):
+        return [self.vid(q, i) for q in range(self.world) for i in range(self.counts[q])]
+
+    def where(self, vid):
+        """(shard, local row) of a vid."""
+        q = shard_of(vid, self.num_parts, self.world)
+        return q, vid // self.world - 1
+
+    def check(self, graph, vids=None):
+        """The placement rule gives this graph the tables the counts claim: a change of the rule fails here."""
+        tables, base = shard_tables(graph, self.num_parts, self.world, vids)
+        assert [len(t) for t in tables] == self.counts, ([len(t) for t in tables], self.counts)
+        assert base == self.base
+        for q, t in enumerate(tables):
+            assert t == [self.vid(q, i) for i in range(self.counts[q])], q
+
+
+def sharded(counts, base_mod=None, vglobal_mod=None):
+    """A Shards of exactly these per-shard row counts (0 included); base_mod: {q: shardBase[q] & 63} and vglobal_mod:
+    vglobal & 63, asserted where the case's name claims them."""
+    sh = Shards(counts)
+    for q, m in (base_mod or {}).items():
+        assert sh.base[q] & 63 == m, (q, sh.base[q], m)
+    assert vglobal_mod is None or sh.vglobal & 63 == vglobal_mod, (sh.vglobal, vglobal_mod)
+    return sh
+
+
+def marker_graph(sh, senders, decoys=(), seed0=None, dup=False, tags=None):
+    """The graph of an exchange case. senders: {(q, i): [(q', i'), ...]}: the out-edges (rank 0; with dup a parallel edge
+    of rank 1 too) whose marks the hop under test exchanges; decoys: the same for rows that are never in the frontier.
+    seed0: a row with an edge to every sender (GO 3 STEPS from it: the senders are hop 2's frontier); without it the
+    senders are the seeds of a GO 2 STEPS. Every other row t (the pool) has exactly one out-edge, to the next pool row in
+    global row order (cyclic), whose p1 is t's global row: the hop after the one under test returns one row per reached
+    vertex, and a further hop again one per vertex. Senders, decoys and seed0 are never targets.
+    Returns (Graph, seeds)."""
+    special = set(senders) | set(dict(decoys)) | ({seed0} if seed0 else set())
+    pool = [(q, i) for q in range(sh.world) for i in range(sh.counts[q]) if (q, i) not in special]
+    edges = []
+    for k, (q, i) in enumerate(pool):
+        nq, ni = pool[(k + 1) % len(pool)]
+        edges.append(edge(sh.vid(q, i), sh.vid(nq, ni), 1, 0, (0, sh.row(q, i), 0)))
+    for src, targets in list(senders.items()) + list(dict(decoys).items()):
+        assert len(set(targets)) == len(targets) and not set(targets) & special, src
+        for t in targets:
+            edges.append(edge(sh.vid(*src), sh.vid(*t), 1, 0))
+            if dup:
+                edges.append(edge(sh.vid(*src), sh.vid(*t), 1, 1))
+    if seed0:
+        edges += [edge(sh.vid(*seed0), sh.vid(*s), 1, 0) for s in sorted(senders)]
+    g = Graph(sh.vids(), edges, types=[1], tags=tags)
+    sh.check(g)
+    return g, [sh.vid(*seed0)] if seed0 else [sh.vid(*s) for s in sorted(senders)]
+
+
+def hop_frontiers(graph, seeds, n):
+    """FORWARD over type e: the frontier (vids) of hops 1 .. n, by the model's rule."""
+    out, frontier = [], list(seeds)
+    for _ in range(n):
+        out.append(frontier)
+        frontier = sorted({w for v in frontier for _, w, _ in graph.rows().get((v, 1), ())})
+    return out
+
+
+def rows_sent(graph, sh, seeds, hop, rank):
+    """The rows of other shards that `rank` marks in hop `hop` (1-based) of a FORWARD GO over e."""
+    mine = [v for v in hop_frontiers(graph, seeds, hop)[hop - 1] if sh.where(v)[0] == rank]
+    return len({w for v in mine for _, w, _ in graph.rows().get((v, 1), ()) if sh.where(w)[0] != rank})
+
+
+def xchg_bitmap_bytes(counts, rank):
+    """exchangeFrontier's lastXchgBytes: a bitmap of every peer's rows, in 64-bit words."""
+    return sum((n + 63) // 64 * 8 for q, n in enumerate(counts) if q != rank)
+
+
+def xchg_list_bytes(world, sent):
+    """exchangeFrontierList's lastXchgBytes: the all-gathered counts and 4 bytes per row sent."""
+    return (world - 1) * world * 8 + 4 * sent
+
+
+def xchg_pull_bytes(counts):
+    """A pulled hop at world > 1: this shard's frontier bitmap, the largest shard's words long, to every peer."""
+    return max((n + 63) // 64 for n in counts) * 8 * (len(counts) - 1)
+
+
+def pulled(model_, q, pull_factor, vglobal):
+    """The intermediate hops (1-based) every shard pulls: the hop's edges over all shards E > 0 and
+    E * 100 >= pull_factor * vglobal (engine.cpp ngx_go, the pull gather)."""
+    return [h for h, E in enumerate(model_.hop_edges, 1) if h < q.n and pull_factor > 0 and E > 0 and
+            E * 100 >= pull_factor * vglobal]
+
+
+# A query of a shard case: the Query, the engine flags (every rank alike), and what proves the path: `xchg` maps a hop
+# (1-based) to "bitmap", "list" or "pull", `counters` the exact increase of the read-only counters on every rank.
+SQ = namedtuple("SQ", "q flags xchg counters")
+ShardCase = namedtuple("ShardCase", "world counts build queries kv")
+SHARD_CASES = {}
+_shard_built = {}
+BITMAP = {"xchg_lists": 0, "pull_factor": 0}
+LISTS = {"xchg_lists": 1, "pull_factor": 0}
+AUTO = {"xchg_lists": -1, "pull_factor": 0}
+SHARD_COUNTERS = ("pull_hops", "xchg_list_hops", "dense_finals", "dst_fetches")
+
+
+def shard_case(name, counts, build, queries, kv=False):
+    assert name not in SHARD_CASES
+    SHARD_CASES[name] = ShardCase(len(counts), list(counts), build, queries, kv)
+
+
+def shard_built(name):
+    """(Graph, default seeds, Shards) of a shard case, built once."""
+    if name not in _shard_built:
+        _shard_built[name] = SHARD_CASES[name].build()
+    return _shard_built[name]
+
+
+def shard_seeds(name, sq):
+    return list(sq.q.seeds) if sq.q.seeds is not None else shard_built(name)[1]
+
+
+def shard_model(name, k):
+    q = SHARD_CASES[name].queries[k].q
+    if ("shard", name, k) not in _models:
+        g = shard_built(name)[0]
+        _models[("shard", name, k)] = model(g, q.form, shard_seeds(name, SHARD_CASES[name].queries[k]), q.over, q.direction,
+                                            q.m, q.n, q.pushdown)
+    return _models[("shard", name, k)]
+
+
+def shard_sentence(name, k):
+    sq = SHARD_CASES[name].queries[k]
+    return sentence(sq.q.form, shard_seeds(name, sq), sq.q.over, sq.q.direction, sq.q.m, sq.q.n)
+
+
+def shard_cases(world):
+    return [n for n in SHARD_CASES if SHARD_CASES[n].world == world]
+
+
+def assert_merged(shard_rows, shard_hop_edges, want, distinct=False, what=""):
+    """shard_rows: per shard its rows as typed cells; shard_hop_edges: per shard its edges scanned per hop. The rows
+    concatenated (for DISTINCT: their set, as graphd applies it to the merged responses) equal the model's as sorted
+    typed rows, and the shards' edges sum to the model's per hop."""
+    merged = [tuple((k, int(v)) for k, v in r) for rows in shard_rows for r in rows]
+    if distinct:
+        merged = list(set(merged))
+    a, b = sorted(merged), typed_rows(want.rows)
+    if a != b:
+        sa, sb = set(a), set(b)
+        raise AssertionError((what, "rows", len(a), len(b), sorted(sa - sb)[:3], sorted(sb - sa)[:3]))
+    hops = len(want.hop_edges)
+    summed = [sum(int(e[h]) if h < len(e) else 0 for e in shard_hop_edges) for h in range(max([hops] + [len(e) for e in shard_hop_edges]))]
+    assert summed == list(want.hop_edges), (what, "hop_edges", summed, want.hop_edges)
+
+
+def _edge_rows(n):
+    """The rows of an n-row range at a wave's, a k_pack block's and a k_pack_list run's and tile's ends."""
+    return sorted({r for r in (0, 63, 64, K_XCHG_BLOCK - 1, K_XCHG_BLOCK, K_LIST_THREADS - 1, K_LIST_THREADS,
+                               K_LIST_TILE - 1, K_LIST_TILE, n - 1) if 0 <= r < n})
+
+
+def _w2_build(n):
+    """World 2, counts [8, n]: five senders on shard 0 whose marks in shard 1's range are none (a row of shard 0
+    instead), row 0, the last row, the edge rows (63 | 64, 255 | 256, 1023 | 1024, 4095 | 4096 where the range has
+    them) and all n rows."""
+    def build():
+        sh = sharded([8, n])
+        senders = {(0, 0): [(0, 7)], (0, 1): [(1, 0)], (0, 2): [(1, n - 1)], (0, 3): [(1, r) for r in _edge_rows(n)],
+                   (0, 4): [(1, r) for r in range(n)]}
+        g, seeds = marker_graph(sh, senders)
+        return g, seeds, sh
+    return build
+
+
+def _w2_queries(n, flags, kind):
+    v = lambda i: [2 * (i + 1) + 1]                                # Shards.vid(0, i) at world 2
+    # in this order: the query that marks every row of the peer, then the one that marks only its last row, on buffers
+    # the first one filled
+    order = [0, 1, 3, 4, 2]
+    qs = [SQ(Q("all", seeds=v(i)), flags, {1: kind}, {"xchg_list_hops": 1 if kind == "list" else 0, "pull_hops": 0})
+          for i in order]
+    return qs
+
+
+BITMAP_N = (1, 63, 64, 65, K_XCHG_BLOCK - 1, K_XCHG_BLOCK, K_XCHG_BLOCK + 1, K_LIST_TILE + 1)
+for _n in BITMAP_N:
+    shard_case("bitmap_w2_%d" % _n, [8, _n], _w2_build(_n), _w2_queries(_n, BITMAP, "bitmap"))
+LIST_N = (1, K_LIST_THREADS - 1, K_LIST_THREADS, K_LIST_THREADS + 1, K_LIST_TILE - 1, K_LIST_TILE, K_LIST_TILE + 1,
+          2 * K_LIST_TILE + 1)
+for _n in LIST_N:
+    shard_case("list_w2_%d" % _n, [8, _n], _w2_build(_n), _w2_queries(_n, LISTS, "list"))
+
+
+def _forms_build(counts):
+    """Senders on every shard that has more than two rows, each marking the first and the last row of every other
+    shard's pool: the graph of the DISTINCT and the REVERSELY query of a world."""
+    def build():
+        sh = sharded(counts)
+        src = [(q, 1) for q in range(sh.world) if sh.counts[q] > 2]
+        senders = {}
+        for s in src:
+            ts = []
+            for q in range(sh.world):
+                rows = [i for i in (0, sh.counts[q] - 1) if 0 <= i < sh.counts[q] and (q, i) not in src]
+                ts += [(q, i) for i in sorted(set(rows))]
+            senders[s] = ts
+        g, seeds = marker_graph(sh, senders)
+        return g, seeds, sh
+    return build
+
+
+def _forms_queries(sh_counts):
+    sh = Shards(sh_counts)
+    target = sh.vid(max(range(len(sh_counts)), key=lambda q: sh_counts[q]), 0)
+    none = {"xchg_list_hops": 0, "pull_hops": 0}
+    return [SQ(Q("all"), BITMAP, {1: "bitmap"}, none), SQ(Q("distinct"), BITMAP, {1: "bitmap"}, none),
+            SQ(Q("all", n=3), BITMAP, {1: "bitmap", 2: "bitmap"}, none),
+            SQ(Q("keys", direction=REVERSELY, seeds=[target]), BITMAP, {1: "bitmap"}, none),
+            SQ(Q("all"), LISTS, {1: "list"}, {"xchg_list_hops": 1, "pull_hops": 0}),
+            SQ(Q("distinct", n=3), LISTS, {1: "list", 2: "list"}, {"xchg_list_hops": 2, "pull_hops": 0})]
+
+
+W8_COUNTS = [3, 1, 0, 58, 1, 64, 5, 70]      # global rows 0 .. 63: shards 0, 1, (2,) 3, 4 and the first row of 5
+shard_case("forms_w2", [70, 129], _forms_build([70, 129]), _forms_queries([70, 129]))
+shard_case("forms_w3_empty", [66, 0, 130], _forms_build([66, 0, 130]), _forms_queries([66, 0, 130]))
+shard_case("forms_w8", W8_COUNTS, _forms_build(W8_COUNTS), _forms_queries(W8_COUNTS))
+
+
+def _triple_build():
+    """World 3: a sender on each shard, all three marking row 64 and row 0 of shard 1 (its owner's sender too), and the
+    senders of shards 0 and 2 each one row of shard 1 the other does not."""
+    sh = sharded([5, 66, 4])
+    senders = {(0, 1): [(1, 64), (1, 0), (1, 63)], (1, 1): [(1, 64), (1, 0)], (2, 1): [(1, 64), (1, 0), (1, 65)]}
+    g, seeds = marker_graph(sh, senders)
+    return g, seeds, sh
+
+
+shard_case("bitmap_w3_triple", [5, 66, 4], _triple_build,
+           [SQ(Q("all"), BITMAP, {1: "bitmap"}, {"xchg_list_hops": 0, "pull_hops": 0}),
+            SQ(Q("all"), LISTS, {1: "list"}, {"xchg_list_hops": 1, "pull_hops": 0})])
+
+
+def _two_senders_build():
+    """World 3, counts [6, 4097, 6]: the senders of shards 0 and 2 both list rows of shard 1: one of them 4000 rows
+    (among them the tile's edge rows), the other 3 (one of them shared), while shard 1 sends nothing: the host
+    collective pads every pair's list to 4000 entries."""
+    sh = sharded([6, K_LIST_TILE + 1, 6])
+    n = K_LIST_TILE + 1
+    many, r = set(_edge_rows(n)), 50
+    while len(many) < 4000:
+        many.add(r)
+        r += 1
+    many = sorted(many)
+    senders = {(0, 1): [(1, r) for r in many], (2, 1): [(1, 5), (1, 4095), (1, 4090)]}
+    g, seeds = marker_graph(sh, senders)
+    return g, seeds, sh
+
+
+shard_case("list_w3_two_senders", [6, K_LIST_TILE + 1, 6], _two_senders_build,
+           [SQ(Q("all"), LISTS, {1: "list"}, {"xchg_list_hops": 1, "pull_hops": 0}),
+            SQ(Q("all"), BITMAP, {1: "bitmap"}, {"xchg_list_hops": 0, "pull_hops": 0})])
+
+AUTO_E = 2
+
+
+def _auto_build(smallest):
+    """The hop's busiest shard scans AUTO_E edges; the smallest shard has `smallest` rows."""
+    def build():
+        sh = sharded([smallest, smallest + 6])
+        g, seeds = marker_graph(sh, {(0, 1): [(1, 0), (1, smallest + 5)]})
+        return g, seeds, sh
+    return build
+
+
+shard_case("auto_w2_bitmap", [K_XCHG_LIST_FACTOR * AUTO_E] * 1 + [K_XCHG_LIST_FACTOR * AUTO_E + 6],
+           _auto_build(K_XCHG_LIST_FACTOR * AUTO_E), [SQ(Q("all"), AUTO, {1: "bitmap"}, {"xchg_list_hops": 0, "pull_hops": 0})])
+shard_case("auto_w2_list", [K_XCHG_LIST_FACTOR * AUTO_E + 1] + [K_XCHG_LIST_FACTOR * AUTO_E + 7],
+           _auto_build(K_XCHG_LIST_FACTOR * AUTO_E + 1), [SQ(Q("all"), AUTO, {1: "list"}, {"xchg_list_hops": 1, "pull_hops": 0})])
+
+
+def _pull_build(counts, base_mod, vglobal_mod):
+    """GO 3 STEPS from seed0: hop 2's frontier is the senders: rows 0, 1, 62 .. 65, n - 2 and n - 1 of every shard (those
+    it has): the first and the last row, and the rows around a word's end, whose bits the repack takes from the next
+    segment word. Rows 2, 61, 66 and n - 3 are decoys with out-edges but outside the frontier. Every sender and decoy
+    has two parallel edges to one pool row of its own, so a lost frontier bit loses a row and a spurious one adds one."""
+    def build():
+        sh = sharded(counts, base_mod, vglobal_mod)
+        big = max(range(sh.world), key=lambda q: sh.counts[q])
+        seed0 = (big, 30)
+        send, decoy = [], []
+        for q in range(sh.world):
+            n = sh.counts[q]
+            s = sorted({i for i in (0, 1, 62, 63, 64, 65, n - 2, n - 1) if 0 <= i < n})
+            send += [(q, i) for i in s]
+            decoy += [(q, i) for i in sorted({2, 61, 66, n - 3}) if 0 <= i < n and i not in s and (q, i) != seed0 and n > 8]
+        special = set(send) | set(decoy) | {seed0}
+        pool = [(q, i) for q in range(sh.world) for i in range(sh.counts[q]) if (q, i) not in special]
+        assert len(pool) >= len(send) + len(decoy), (len(pool), len(send), len(decoy))
+        # the senders' targets spread over the whole pool (and so over every shard that has pool rows), each decoy's
+        # target the pool row after a sender's
+        at = [k * len(pool) // len(send) for k in range(len(send))]
+        assert len(set(at)) == len(at) and all(b - a >= 2 for a, b in zip(at, at[1:])) and at[-1] + 1 < len(pool)
+        senders = {s: [pool[at[k]]] for k, s in enumerate(send)}
+        decoys = {d: [pool[at[k * len(send) // max(len(decoy), 1)] + 1]] for k, d in enumerate(decoy)}
+        assert {q for ts in senders.values() for q, _ in ts} >= {q for q in range(sh.world) if sh.counts[q] >= 40}
+        g, seeds = marker_graph(sh, senders, decoys, seed0=seed0, dup=True)
+        assert (big, sh.counts[big] - 1) in senders
+        return g, seeds, sh
+    return build
+
+
+def _pull_queries(counts):
+    """pull_factor 1: hop 2 (and hop 1 where its edges suffice) is pulled, then the dense final hop, its totals sized
+    on the device and on the host; then GO 4 STEPS with the pull_factor that hop 2's edges reach and hop 3's do not:
+    a pulled hop followed by a pushed one. The expected counters come from the model (tests/test_gpu_go_shards.py)."""
+    return [SQ(Q("all", n=3), {"pull_factor": 1, "xchg_lists": 0, "dense_world_dev": 1}, None, None),
+            SQ(Q("all", n=3), {"pull_factor": 1, "xchg_lists": 0, "dense_world_dev": 0}, None, None),
+            SQ(Q("all", n=4), {"pull_factor": "hop2", "xchg_lists": 0, "dense_world_dev": 1}, None, None)]
+
+
+PULL_SHAPES = {
+    "pull_w2_base0": ([64, 40], {1: 0}, 40),          # shardBase[1] & 63 == 0; vglobal no multiple of 64
+    "pull_w2_base1": ([65, 63], {1: 1}, 0),           # == 1; vglobal == 128
+    "pull_w2_base63": ([63, 128], {1: 63}, 63),       # == 63; the largest shard ends with its last word's last bit
+    "pull_w3_empty": ([70, 0, 122], {1: 6, 2: 6}, 0),
+    "pull_w8": (W8_COUNTS, {3: 4, 5: 63, 7: 4}, 10),   # output word 0 holds four shards with rows and part of a fifth
+}
+for _name, (_c, _b, _v) in PULL_SHAPES.items():
+    shard_case(_name, _c, _pull_build(_c, _b, _v), _pull_queries(_c))
+
+
+def pull_factor_hop2(name, k):
+    """The pull_factor that pulls hop 2 of a GO 4 STEPS and pushes its hop 3: the largest with E2 * 100 >= pf * vglobal."""
+    m = shard_model(name, k)
+    sh = shard_built(name)[2]
+    pf = m.hop_edges[1] * 100 // sh.vglobal
+    assert pf >= 1 and m.hop_edges[2] * 100 < pf * sh.vglobal and m.hop_edges[0] * 100 < pf * sh.vglobal, (name, pf, m.hop_edges)
+    return pf
+
+
+def shard_flags(name, k):
+    f = dict(SHARD_CASES[name].queries[k].flags)
+    if f.get("pull_factor") == "hop2":
+        f["pull_factor"] = pull_factor_hop2(name, k)
+    return f
+
+
+def _tags_build(counts, where):
+    """GO 2 STEPS from seed0 (shard 0) over senders on every shard with rows to spare; the final hop's destinations are
+    on the sender's own shard only (`self`), on the next shard only (`peer`), or on every shard (`all`). A third of the
+    vertices have no tag row, a sender and a destination among them; negative x fails the WHERE. Every vertex has an
+    edge, so a KV load knows every row."""
+    def build():
+        sh = sharded(counts)
+        W = sh.world
+        src = [(q, 1) for q in range(W) if sh.counts[q] > 3]
+        seed0 = (src[0][0], 2)
+        senders = {}
+        for k, s in enumerate(src):
+            q = s[0]
+            owners = {"self": [q], "peer": [src[(k + 1) % len(src)][0]], "all": [p for p in range(W) if sh.counts[p]]}[where]
+            senders[s] = [(p, i) for p in owners for i in sorted({0, sh.counts[p] - 1, 3 % sh.counts[p]})
+                          if (p, i) not in src and (p, i) != seed0]
+        g, seeds = marker_graph(sh, senders, seed0=seed0)
+        tags = {}
+        for n_, v in enumerate(g.vids):
+            if n_ % 3 != 2:
+                tags[v] = (v * 37) % 1000 - 200
+        lacking = set(g.vids) - set(tags)
+        ends = {sh.vid(*t) for ts in senders.values() for t in ts}
+        tags.pop(sh.vid(*src[-1]), None)                          # a source without a tag row
+        tags.pop(sorted(ends)[0], None)                           # a destination without one
+        assert lacking and ends - set(tags) and ends & set(tags)
+        g.tags = tags
+        sh.check(g, kv_vertices(g))
+        return g, seeds, sh
+    return build
+
+
+def _tags_queries():
+    return [SQ(Q("tags"), {"dst_props": 0, "xchg_lists": 0, "pull_factor": 0}, {1: "bitmap"}, {"dst_fetches": 0}),
+            SQ(Q("tags"), {"dst_props": 1, "xchg_lists": 0, "pull_factor": 0}, {1: "bitmap"}, {"dst_fetches": 1})]
+
+
+shard_case("tags_w2_self", [9, 14], _tags_build([9, 14], "self"), _tags_queries(), kv=True)
+shard_case("tags_w2_peer", [9, 14], _tags_build([9, 14], "peer"), _tags_queries(), kv=True)
+shard_case("tags_w3_all", [7, 70, 12], _tags_build([7, 70, 12], "all"), _tags_queries(), kv=True)
+shard_case("tags_w8_all", W8_COUNTS, _tags_build(W8_COUNTS, "all"), _tags_queries(), kv=True)

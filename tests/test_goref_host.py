@@ -28,6 +28,15 @@ def test_constants_match_the_headers():
     assert re.search(r"constexpr int kSparseSub = CE / WG;", open(os.path.join(CSRC, "kernels.hip")).read())
     assert re.search(r"constexpr int CE = static_cast<int>\(kChunk\);", open(os.path.join(CSRC, "final_kernels.h")).read())
     assert goref.K_SPARSE_SUB == 8
+    # the exchange's named constants are the ones the kernels and the driver use
+    hip = open(os.path.join(CSRC, "kernels.hip")).read()
+    for use in (r"__launch_bounds__\(kXchgBlock\) void k_pack\(", r"__launch_bounds__\(kXchgBlock\) void k_merge\(",
+                r"__launch_bounds__\(kListThreads\) void k_pack_list\(", r"blockIdx\.x\) \* kListTile;",
+                r"kListTile == 4 \* kListThreads"):
+        assert re.search(use, hip), use
+    assert re.search(r"kXchgListFactor \* eMaxShard < minPeer", open(os.path.join(CSRC, "engine.cpp")).read())
+    assert (goref.K_XCHG_BLOCK, goref.K_LIST_THREADS, goref.K_LIST_TILE, goref.K_XCHG_LIST_FACTOR, goref.K_MAX_WORLD) == \
+        (256, 1024, 4096, 32, 64)
 
 
 @pytest.mark.parametrize("name", sorted(goref.CASES))
