@@ -3217,6 +3217,7 @@ void jitSlotConsts(JitQuery& jq, std::vector<int64_t>& kc, std::vector<uint32_t>
 // (GoExecutor.h:189-207) — so that every record hop's rows can be attributed to their roots
 // (getRoots, GoExecutor.cpp:1317-1330). World 1, push hops, no storage mask (the caller walks per
 // root otherwise: runGo fails such a walk with NGX_E_UNSUPPORTED before any row).
+static_assert(kRootBatch == 64, "a row's root set is one 64-bit word");
 struct RootWalk {
     std::unordered_map<int64_t, uint64_t> bitsOf;              // start vid -> its root bit
     // WHERE / YIELD read $-.x: every record hop's entries are (frontier row, input row) pairs, one per
@@ -4764,6 +4765,7 @@ int32_t runPipe(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R) 
             for (size_t i = 0; i < x.size(); i++) a[i] += x[i];
         };
         addv(R.hopFrontier, S.hopFrontier); addv(R.hopEdges, S.hopEdges); addv(R.hopNext, S.hopNext);
+        addv(R.hopXchg, S.hopXchg);                              // world > 1: the walks' exchanges, frontier and root sets
         const uint64_t base = R.strings.size();
         R.strings += S.strings;
         for (uint64_t r = 0; r < S.r.nrows; r++) {
@@ -4806,8 +4808,8 @@ int32_t runPipe(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R) 
         // shards together) falls back to a walk per vid, before any row is kept.
         bool batched = true;
         std::vector<std::pair<std::unique_ptr<GoResultHolder>, std::unique_ptr<RootWalk>>> walks;
-        for (size_t b0 = 0; batched && b0 < vids.size(); b0 += 64) {
-            const size_t n = std::min<size_t>(64, vids.size() - b0);
+        for (size_t b0 = 0; batched && b0 < vids.size(); b0 += kRootBatch) {
+            const size_t n = std::min<size_t>(kRootBatch, vids.size() - b0);
             auto rw = std::make_unique<RootWalk>();
             for (size_t j = 0; j < n; j++) rw->bitsOf[vids[b0 + j]] = 1ULL << j;
             auto S = std::make_unique<GoResultHolder>();
@@ -4826,7 +4828,7 @@ int32_t runPipe(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R) 
             for (size_t w = 0; w < walks.size(); w++) {
                 GoResultHolder& S = *walks[w].first;
                 const RootWalk& rw = *walks[w].second;
-                const size_t b0 = w * 64;
+                const size_t b0 = w * kRootBatch;
                 absorb(S, [&](uint64_t r) {
                     for (const RootWalk::Hop& hop : rw.record) {
                         if (r < hop.rowBase || r >= hop.rowBase + hop.rows) continue;
@@ -4901,11 +4903,11 @@ int32_t runPipe(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R) 
             HIP_OK(hipMemcpyAsync(dDesc, desc.data(), nc * sizeof(DInputCol), hipMemcpyHostToDevice, c->stream));
             HIP_OK(hipStreamSynchronize(c->stream));
             inputDev = dDesc;
-            rowsOfBit.resize((vids.size() + 63) / 64);
+            rowsOfBit.resize((vids.size() + kRootBatch - 1) / kRootBatch);
         }
-        for (size_t b0 = 0; batched && b0 < vids.size(); b0 += 64) {
-            const size_t n = std::min<size_t>(64, vids.size() - b0);
-            auto& rob = rowsOfBit[b0 / 64];
+        for (size_t b0 = 0; batched && b0 < vids.size(); b0 += kRootBatch) {
+            const size_t n = std::min<size_t>(kRootBatch, vids.size() - b0);
+            auto& rob = rowsOfBit[b0 / kRootBatch];
             rob.resize(n);
             auto rwk = std::make_unique<RootWalk>();
             for (size_t j = 0; j < n; j++) {

@@ -82,6 +82,9 @@ __device__ __forceinline__ uint32_t vindexFind(const VIndex& idx, int32_t part, 
 // seed hop (n seeds, n * hs.n <= kSeedFuseMax entries): launchSeedFrontierCf below
 constexpr uint64_t kSeedFuseMax = 4096;
 
+// multi-root walk (engine.cpp runPipe): the roots of one walk, one bit of a row's 64-bit root set each
+constexpr uint64_t kRootBatch = 64;
+
 int launchIndexLookup(const int32_t* qpart, const int64_t* qvid, uint64_t n, VIndex idx, uint32_t* out, hipStream_t s);
 int launchLookup(const int32_t* qpart, const int64_t* qvid, uint64_t n, const int32_t* vpart, const int64_t* vid,
                  uint64_t V, uint32_t* out, hipStream_t s);

@@ -32,6 +32,7 @@ Cells are `(kind, value)` as the engine and the oracle hand them out: "id" for `
 `_type` and INT properties.
 """
 import random
+import struct
 from collections import namedtuple
 
 import numpy as np
@@ -58,12 +59,14 @@ K_LIST_THREADS = 1024           # kernels.h   kListThreads (k_pack_list)
 K_LIST_TILE = 4096              # kernels.h   kListTile (k_pack_list rows per workgroup)
 K_XCHG_LIST_FACTOR = 32         # kernels.h   kXchgListFactor (lists iff 32 * E of the busiest shard < smallest shard)
 K_MAX_WORLD = 64                # kernels.h   kMaxWorld
+K_ROOT_BATCH = 64               # kernels.h   kRootBatch (roots of one multi-root walk: one bit of a row's set each)
+K_TILE = 4096                   # kargs.h     kTile (the degree scan's tile, over a record hop's (row, input row) entries)
 CONSTANTS = {
     "kernels.h": {"kSeedFuseMax": K_SEED_FUSE_MAX, "kPullK": K_PULL_K, "kPullWindow": K_PULL_WINDOW,
                   "kPullSeg": K_PULL_SEG, "kPullMaxSlots": K_PULL_MAX_SLOTS, "kCompactTile": K_COMPACT_TILE,
                   "kXchgBlock": K_XCHG_BLOCK, "kListThreads": K_LIST_THREADS, "kListTile": K_LIST_TILE,
-                  "kXchgListFactor": K_XCHG_LIST_FACTOR, "kMaxWorld": K_MAX_WORLD},
-    "kargs.h": {"kChunk": K_CHUNK, "kResvShift": K_RESV_SHIFT, "kResvGroups": K_RESV_GROUPS},
+                  "kXchgListFactor": K_XCHG_LIST_FACTOR, "kMaxWorld": K_MAX_WORLD, "kRootBatch": K_ROOT_BATCH},
+    "kargs.h": {"kChunk": K_CHUNK, "kResvShift": K_RESV_SHIFT, "kResvGroups": K_RESV_GROUPS, "kTile": K_TILE},
     "final_kernels.h": {"WG": K_WG},
 }
 
@@ -241,8 +244,18 @@ def column_kinds(form):
 
 
 # ----------------------------------------------------------------------------- the comparator
+def typed_cell(k, v):
+    """A cell as the comparator sees it: a string exactly, a double by its bits, everything else as an integer."""
+    if k == "str":
+        assert isinstance(v, str), (k, v)
+        return (k, v)
+    if k in ("double", "float"):
+        return (k, struct.unpack("<q", struct.pack("<d", v))[0])
+    return (k, int(v))
+
+
 def typed_rows(rows):
-    return sorted(tuple((k, int(v)) for k, v in r) for r in rows)
+    return sorted(tuple(typed_cell(k, v) for k, v in r) for r in rows)
 
 
 def assert_same(got, want, what=""):
@@ -253,7 +266,12 @@ def assert_same(got, want, what=""):
     assert [int(x) for x in edges] == list(want.hop_edges), (what, "hop_edges", list(edges), want.hop_edges)
     assert [int(x) for x in got.hop_frontier] == list(want.hop_frontier), (what, "hop_frontier", list(got.hop_frontier),
                                                                            want.hop_frontier)
-    a, b = typed_rows(got.rows), typed_rows(want.rows)
+    assert_rows(got.rows, want.rows, what)
+
+
+def assert_rows(got, want, what=""):
+    """Two lists of rows of typed cells are the same multiset."""
+    a, b = typed_rows(got), typed_rows(want)
     if a != b:
         sa, sb = set(a), set(b)
         raise AssertionError((what, "rows", len(a), len(b), sorted(sa - sb)[:3], sorted(sb - sa)[:3]))
@@ -1061,7 +1079,7 @@ def assert_merged(shard_rows, shard_hop_edges, want, distinct=False, what=""):
     """shard_rows: per shard its rows as typed cells; shard_hop_edges: per shard its edges scanned per hop. The rows
     concatenated (for DISTINCT: their set, as graphd applies it to the merged responses) equal the model's as sorted
     typed rows, and the shards' edges sum to the model's per hop."""
-    merged = [tuple((k, int(v)) for k, v in r) for rows in shard_rows for r in rows]
+    merged = [tuple(typed_cell(k, v) for k, v in r) for rows in shard_rows for r in rows]
     if distinct:
         merged = list(set(merged))
     a, b = sorted(merged), typed_rows(want.rows)
@@ -1306,3 +1324,384 @@ shard_case("tags_w2_self", [9, 14], _tags_build([9, 14], "self"), _tags_queries(
 shard_case("tags_w2_peer", [9, 14], _tags_build([9, 14], "peer"), _tags_queries(), kv=True)
 shard_case("tags_w3_all", [7, 70, 12], _tags_build([7, 70, 12], "all"), _tags_queries(), kv=True)
 shard_case("tags_w8_all", W8_COUNTS, _tags_build(W8_COUNTS, "all"), _tags_queries(), kv=True)
+
+
+# ----------------------------------------------------------------------------- pipes: GO ... FROM $-.id / $var.id
+# The reference rule (GoExecutor.cpp:471-509 setupStarts, :1317-1330 getRoots + rowsOfVids): an edge row is emitted once
+# per input row whose vid is one of the row's roots, `$-.x` bound to that input row. Per root that is a GO from the root
+# alone, so: per input row i with vid v_i the rows are exactly those of `GO ... FROM v_i`, `$-.x` bound to row i's
+# cells; the result is the concatenation over the input rows; YIELD DISTINCT is one set over the whole result. An input
+# vid that is no vertex, or has no edges, contributes nothing. `pipe` is that loop over `go`, nothing else: no root
+# sets, no batches.
+PIPE_COLS = ("id", "k", "w", "s", "d")                            # the vid column, two INT, a STRING, a DOUBLE
+T_DOUBLE, T_STRING = 5, 6                                         # pipeline.T_DOUBLE / T_STRING (asserted by the host test)
+
+
+def pipe_input(rows, vid_type=kvfmt.VID):
+    """rows: (vid, k, w, s, d) tuples -> the Interim a pipe's right side reads. vid_type: the vid column as VID or INT."""
+    from nebula_amd import pipeline
+    kind = "id" if vid_type == kvfmt.VID else "int"
+    return pipeline.Interim(list(PIPE_COLS), [vid_type, kvfmt.INT, kvfmt.INT, T_STRING, T_DOUBLE],
+                            [((kind, v), ("int", k), ("int", w), ("str", s), ("double", d)) for v, k, w, s, d in rows])
+
+
+def input_row(v, j, dup=0, w=None):
+    """The input row of root j (its dup-th): k is j mod K_ROOT_BATCH (roots 0 and 64 share it), w differs per duplicate."""
+    return (v, j % K_ROOT_BATCH, (j * 37 + dup * 11) % 100 if w is None else w, "r%d.%d" % (j, dup), j + dup / 4.0)
+
+
+def _pe(kind, name, k=0):
+    return lambda over: (lambda row, inp: (kind, _of(row, over[k], name)))
+
+
+def _pin(name):
+    return lambda over: (lambda row, inp: inp[name])
+
+
+# A pipe form: as Form, but the callables also receive the input row ({column name: cell}); reads: WHERE or YIELD read
+# the input (the device then keys entries by (frontier row, input row)); var: the sentence reads `$var` instead of `$-`.
+PipeForm = namedtuple("PipeForm", "name tail where yields distinct min_over reads var")
+PIPE_FORMS = {f.name: f for f in [
+    PipeForm("all", "YIELD {a}._dst, {a}.p1", None, [_pe("id", "_dst"), _pe("int", "p1")], False, 1, False, None),
+    PipeForm("all_d", "YIELD DISTINCT {a}._dst, {a}.p1", None, [_pe("id", "_dst"), _pe("int", "p1")], True, 1, False, None),
+    PipeForm("keys", "YIELD {a}._src, {a}._dst, {a}._type", None,
+             [_pe("id", "_src"), _pe("id", "_dst"), _pe("int", "_type")], False, 1, False, None),
+    PipeForm("k", "YIELD $-.k, {a}._dst", None, [_pin("k"), _pe("id", "_dst")], False, 1, True, None),
+    PipeForm("k_d", "YIELD DISTINCT $-.k, {a}._dst", None, [_pin("k"), _pe("id", "_dst")], True, 1, True, None),
+    PipeForm("w", "WHERE {a}.p0 >= $-.w YIELD $-.w, $-.s, $-.d, {a}._dst, {a}.p0",
+             lambda over: (lambda row, inp: _of(row, over[0], "p0") >= inp["w"][1]),
+             [_pin("w"), _pin("s"), _pin("d"), _pe("id", "_dst"), _pe("int", "p0")], False, 1, True, None),
+    PipeForm("two", "YIELD $-.k, {a}._dst, {b}._dst, {a}.p0, {b}.p0", None,
+             [_pin("k"), _pe("id", "_dst"), _pe("id", "_dst", 1), _pe("int", "p0"), _pe("int", "p0", 1)], False, 2, True, None),
+    PipeForm("var", "WHERE {a}.p0 >= $v.w YIELD $v.w, $v.s, {a}._dst",
+             lambda over: (lambda row, inp: _of(row, over[0], "p0") >= inp["w"][1]),
+             [_pin("w"), _pin("s"), _pe("id", "_dst")], False, 1, True, "v"),
+]}
+
+
+def pipe_sentence(form, over, direction=FORWARD, m=None, n=1):
+    f = PIPE_FORMS[form]
+    assert len(over) >= f.min_over
+    steps = "%d STEPS" % n if m is None else "%d TO %d STEPS" % (m, n)
+    tail = f.tail.replace("{a}", over[0]).replace("{b}", over[1] if len(over) > 1 else over[0])
+    return "GO %s FROM %s.id OVER %s%s %s" % (steps, "$" + f.var if f.var else "$-", ", ".join(over), _DIR[direction], tail)
+
+
+def pipe(graph, form, inp, over, direction=FORWARD, m=None, n=1):
+    """The rows of the pipe form over the input `inp` (an Interim with a column `id`): see the section's comment."""
+    f = PIPE_FORMS[form]
+    types = [TYPE_OF[x] for x in over]
+    where = f.where(types) if f.where else None
+    ys = [y(types) for y in f.yields]
+    at = inp.names.index("id")
+    out = []
+    for cells in inp.rows:
+        env = dict(zip(inp.names, cells))
+        out += go(graph, [cells[at][1]], types, direction, n if m is None else m, n,
+                  (lambda row, env=env: where(row, env)) if where else None,
+                  [(lambda row, y=y, env=env: y(row, env)) for y in ys]).rows
+    if f.distinct:
+        out = list(dict.fromkeys(out))
+    return out
+
+
+Plan = namedtuple("Plan", "walks hop_edges hop_frontier")
+
+
+def pipe_plan(graph, form, inp, over, direction=FORWARD, m=None, n=1, fallback=False):
+    """What the device plan scans (engine.cpp runPipe), for hop_edges / hop_frontier and the pipe_walks counter only:
+    no input row: nothing; one step and no read of the input: one plain walk from the distinct vids (first-seen order);
+    otherwise one walk per K_ROOT_BATCH distinct vids from their union; fallback (a storage mask: the walk cannot be
+    keyed by root): one walk per distinct vid, or per input row where the input is read. The statistics add up."""
+    f = PIPE_FORMS[form]
+    types = [TYPE_OF[x] for x in over]
+    at = inp.names.index("id")
+    vids = list(dict.fromkeys(c[at][1] for c in inp.rows))
+    if not vids:
+        return Plan(0, [], [])
+    if not f.reads and n == 1:
+        starts = [vids]
+    elif fallback:
+        starts = [[c[at][1]] for c in inp.rows] if f.reads else [[v] for v in vids]
+    else:
+        starts = [vids[b:b + K_ROOT_BATCH] for b in range(0, len(vids), K_ROOT_BATCH)]
+    he, hf = [], []
+    for s in starts:
+        r = go(graph, s, types, direction, n, n, None, [])
+        for acc, x in ((he, r.hop_edges), (hf, r.hop_frontier)):
+            acc += [0] * (len(x) - len(acc))
+            for h, v in enumerate(x):
+                acc[h] += v
+    return Plan(len(starts), he, hf)
+
+
+# ---- shaped graphs and inputs (every generator returns (Graph, {input name: Interim}))
+def _rotated(n, by=5):
+    return [(j + by) % n for j in range(n)]
+
+
+def roots_graph(R, same_mid=None, vid_type=kvfmt.VID, rotate=5):
+    """R roots (vid 1 + j), each with a private path root -> mid (10000 + j) -> leaf (20000 + j) whose edges carry
+    p1 = j and p0 = j % 100; same_mid {j: i}: root j points at root i's mid instead (and has no mid of its own). One
+    input row per root, in an order rotated by `rotate` so that a root's bit is not its row."""
+    same_mid = same_mid or {}
+    edges = []
+    for j in range(R):
+        mj = same_mid.get(j, j)
+        edges.append(edge(1 + j, 10000 + mj, 1, 0, (j % 100, j, 0)))
+        if mj == j:
+            edges.append(edge(10000 + j, 20000 + j, 1, 0, (j % 100, j, -j)))
+    vids = {v for e_ in edges for v in e_[:2]}
+    return Graph(vids, edges), {"in": pipe_input([input_row(1 + j, j) for j in _rotated(R, rotate)], vid_type)}
+
+
+CONVERGE_ROOTS = K_ROOT_BATCH
+HUB, SIDE = 500, 501
+
+
+def converge_mults(m_last):
+    """Input rows per root: 1, 2, 3 in turn, the last root m_last."""
+    return [1 + j % 3 for j in range(CONVERGE_ROOTS - 1)] + [m_last]
+
+
+def converge_graph(m_last, D, flip=False, two=False):
+    """K_ROOT_BATCH roots (vids 1 ..) of one batch that all reach HUB at hop 1; HUB has D out-edges (p0 = i % 20,
+    p1 = i) to leaves 1000 + i. flip: every edge reversed (for REVERSELY). two: HUB also has D edges of type f to
+    leaves 2000 + i, and every root also points (type e) at SIDE, which has two edges of type f and none of type e.
+    The input rows of a root are spread over the input (by duplicate, then by root) and differ in w (0 .. 19)."""
+    mk = (lambda a, b, t, p: edge(b, a, t, 0, p)) if flip else (lambda a, b, t, p: edge(a, b, t, 0, p))
+    edges = [mk(1 + j, HUB, 1, (j % 100, j, 0)) for j in range(CONVERGE_ROOTS)]
+    edges += [mk(HUB, 1000 + i, 1, (i % 20, i, 0)) for i in range(D)]
+    if two:
+        edges += [mk(HUB, 2000 + i, 2, (i % 20, 100 + i, 0)) for i in range(D)]
+        edges += [mk(1 + j, SIDE, 1, (j % 100, j, 1)) for j in range(CONVERGE_ROOTS)]
+        edges += [mk(SIDE, 3000 + i, 2, (5 * i, 200 + i, 0)) for i in range(2)]
+    mults = converge_mults(m_last)
+    order = sorted((dup, j) for j in range(CONVERGE_ROOTS) for dup in range(mults[j]))
+    rows = [input_row(1 + j, j, dup, w=(j * 5 + dup * 3) % 20) for dup, j in order]
+    vids = {v for e_ in edges for v in e_[:2]}
+    return Graph(vids, edges, types=[1, 2] if two else [1]), {"in": pipe_input(rows)}
+
+
+# (the last root's input rows, D): sum of the multiplicities x D = K_CHUNK - 1, K_CHUNK, K_CHUNK + 1 and 128 x 17 (a
+# chunk boundary inside one entry's run of 17 edges); the host test asserts the products
+CONVERGE_SHAPES = {"below": (K_CHUNK - 1 - 126, 1), "exact": (2, 16), "above": (683 - 126, 3), "inside": (2, 17)}
+
+
+def entries_graph(N, deg):
+    """One vid (7) in N input rows with w = the row's number; its `deg` out-edges have p0 = N // 2, N, 0."""
+    edges = [edge(7, 100 + i, 1, 0, ((N // 2, N, 0)[i], i, 0)) for i in range(deg)]
+    rows = [(7, r % 1000, r, "s%d" % r, r * 0.5) for r in range(N)]
+    return Graph([7] + [100 + i for i in range(deg)], edges), {"in": pipe_input(rows)}
+
+
+def ring_graph():
+    """A directed ring 1 -> 2 -> ... -> 5 -> 1 (p1 = the source, p0 = 10 x the source). Inputs: every vertex a root (two
+    rows for vertex 2); roots 1 and 3 only."""
+    edges = [edge(i, i % 5 + 1, 1, 0, (10 * i, i, 0)) for i in range(1, 6)]
+    five = [input_row(i, i - 1, 0, w=7 * i) for i in range(1, 6)] + [input_row(2, 1, 1, w=0)]
+    two = [input_row(1, 0, 0, w=15), input_row(3, 2, 0, w=0)]
+    return Graph(range(1, 6), edges), {"five": pipe_input(five), "two": pipe_input(two)}
+
+
+def dying_graph():
+    """A live chain 1 -> 2 -> 3 -> {4, 6} -> 5; C = 10 -> 11 and 11 has no out-edge (its walk ends at hop 1 of 3);
+    B = 20 has no edge at all; 999 and 3000 .. 3031 are no vertices; 4000 .. 4031 are vertices without edges; 70 roots
+    5000 + j -> 2 join the chain. Inputs, in the order the queries use them: `mixed` (a dead vid, B, C and the live
+    root in one batch, C and the live root twice), `dead_live` (a first batch of 64 roots that all die at hop 1 with no
+    edge scanned, then three live ones), `many` (71 roots), `one`."""
+    edges = [edge(1, 2, 1, 0, (50, 1, 0)), edge(2, 3, 1, 0, (60, 2, 0)), edge(3, 4, 1, 0, (70, 3, 0)),
+             edge(3, 6, 1, 0, (5, 33, 0)), edge(4, 5, 1, 0, (80, 4, 0)), edge(6, 5, 1, 0, (90, 6, 0)),
+             edge(10, 11, 1, 0, (40, 10, 0))]
+    edges += [edge(5000 + j, 2, 1, 0, (j, 5000 + j, 0)) for j in range(70)]
+    vids = {v for e_ in edges for v in e_[:2]} | {20} | {4000 + i for i in range(32)}
+    mixed = [input_row(999, 0), input_row(20, 1), input_row(10, 2), input_row(1, 3), input_row(10, 2, 1), input_row(1, 3, 1, w=0)]
+    dead = [3000 + i for i in range(32)] + [4000 + i for i in range(32)]
+    dead_live = [input_row(v, j) for j, v in enumerate(dead)] + [input_row(1, 64, 0, w=0), input_row(5000, 65), input_row(5001, 66)]
+    many = [input_row(5000 + j, j, 0, w=j) for j in range(70)] + [input_row(1, 70, 0, w=55)]
+    return Graph(vids, edges), {"mixed": pipe_input(mixed), "dead_live": pipe_input(dead_live), "many": pipe_input(many),
+                                "one": pipe_input([input_row(1, 0, 0, w=60)])}
+
+
+ONEWALK_V = K_SEED_FUSE_MAX + 1
+
+
+def onewalk_graph():
+    """K_SEED_FUSE_MAX + 1 vertices, every one in the input, once or three times; one or two out-edges each."""
+    N = ONEWALK_V
+    keys = set()
+    for i in range(N):
+        keys.add((i + 1, i * 7 % N + 1))
+        if i % 3 == 0:
+            keys.add((i + 1, (i * 11 + 1) % N + 1))
+    edges = [edge(a, b) for a, b in sorted(keys)]
+    rows = [input_row(1 + j, j, dup) for dup in range(3) for j in range(N) if dup == 0 or j % 2]
+    return Graph(range(1, N + 1), edges), {"in": pipe_input(rows)}
+
+
+LONG_S = "".join(chr(33 + i) for i in range(63)).replace('"', "x").replace("\\", "y")
+
+
+def columns_graph():
+    """Three private paths; the vid column typed VID and typed INT; w at INT64_MIN, -1, 0 and INT64_MAX; an empty and a
+    63-byte string; -0.0 and 0.0 as doubles."""
+    g, _ = roots_graph(3)
+    rows = [(1, 0, INT64_MIN, "", -0.0), (1, 1, -1, LONG_S, 0.0), (2, 2, 0, "a", 1.5), (2, 3, INT64_MAX, "b", -2.25),
+            (3, 4, 2, "", 1e300), (3, 5, 3, LONG_S, -0.0)]
+    assert len(LONG_S.encode()) == 63
+    return g, {"vid": pipe_input(rows, kvfmt.VID), "int": pipe_input(rows, kvfmt.INT)}
+
+
+# ---- the cases (tests/test_gpu_pipe_shapes.py on the device, tests/test_pipe_shapes_host.py against the oracle)
+PQ = namedtuple("PQ", "form over direction m n inp")
+
+
+def P(form, over=("e",), direction=FORWARD, m=None, n=2, inp="in"):
+    return PQ(form, tuple(over), direction, m, n, inp)
+
+
+# cap: max_edge_returned_per_vertex of the engine (0: unset); a cap makes the walks fall back (pipe_plan's fallback)
+PipeCase = namedtuple("PipeCase", "build queries cap")
+PIPE_CASES = {}
+_pipe_built = {}
+
+
+def pipe_case(name, build, queries, cap=0):
+    assert name not in PIPE_CASES
+    PIPE_CASES[name] = PipeCase(build, queries, cap)
+
+
+def pipe_built(name):
+    if name not in _pipe_built:
+        _pipe_built[name] = PIPE_CASES[name].build()
+    return _pipe_built[name]
+
+
+def pipe_case_sentence(name, k):
+    q = PIPE_CASES[name].queries[k]
+    return pipe_sentence(q.form, q.over, q.direction, q.m, q.n)
+
+
+def pipe_case_model(name, k):
+    """Model(rows of `pipe`, hop_edges and hop_frontier of `pipe_plan`) of query k, computed once, and the walks."""
+    if ("pipe", name, k) not in _models:
+        g, inputs = pipe_built(name)
+        q = PIPE_CASES[name].queries[k]
+        plan = pipe_plan(g, q.form, inputs[q.inp], q.over, q.direction, q.m, q.n, PIPE_CASES[name].cap > 0)
+        _models[("pipe", name, k)] = (Model(pipe(g, q.form, inputs[q.inp], q.over, q.direction, q.m, q.n), plan.hop_edges,
+                                            plan.hop_frontier), plan.walks)
+    return _models[("pipe", name, k)]
+
+
+ROOT_COUNTS = (1, K_ROOT_BATCH - 1, K_ROOT_BATCH, K_ROOT_BATCH + 1, 2 * K_ROOT_BATCH, 2 * K_ROOT_BATCH + 1)
+for _n in ROOT_COUNTS:
+    pipe_case("roots%d" % _n, (lambda n: lambda: roots_graph(n))(_n), [P("all"), P("k"), P("w"), P("var"), P("all", m=1, n=2)])
+for _name, (_m, _d) in CONVERGE_SHAPES.items():
+    pipe_case("converge_" + _name, (lambda m, d: lambda: converge_graph(m, d))(_m, _d), [P("all"), P("w"), P("k")])
+pipe_case("converge_reversely", lambda: converge_graph(1, 5, flip=True),
+          [P("keys", direction=REVERSELY), P("w", direction=REVERSELY), P("keys", direction=REVERSELY, m=1, n=2)])
+pipe_case("converge_bidirect", lambda: converge_graph(1, 5),
+          [P("keys", direction=BIDIRECT), P("w", direction=BIDIRECT), P("k", direction=BIDIRECT, m=1, n=2)])
+pipe_case("converge_two_types", lambda: converge_graph(1, 5, two=True),
+          [P("two", "ef"), P("two", "fe"), P("all", "ef"), P("two", "ef", m=1, n=2)])
+ENTRY_ROWS = (K_TILE - 1, K_TILE, K_TILE + 1)
+for _n in ENTRY_ROWS:
+    for _d in (1, 3):
+        pipe_case("entries%d_deg%d" % (_n, _d), (lambda n, d: lambda: entries_graph(n, d))(_n, _d), [P("w", n=1), P("k", n=1)])
+pipe_case("ring", ring_graph, [P(f, m=1, n=4, inp=i) for i in ("five", "two") for f in ("all", "k", "w")] +
+          [P("k", n=4, inp="five"), P("all", n=3, inp="two")])
+pipe_case("dying", dying_graph, [P(f, m=m, n=3, inp=i) for i in ("mixed", "dead_live", "many", "one")
+                                 for f, m in (("all", None), ("w", None), ("k", 1))])
+pipe_case("distinct_across", lambda: roots_graph(K_ROOT_BATCH + 1, {K_ROOT_BATCH: 0}, rotate=0), [P("all_d"), P("all"), P("k_d"), P("k")])
+pipe_case("onewalk", onewalk_graph, [P("all", n=1), P("keys", direction=REVERSELY, n=1), P("keys", direction=BIDIRECT, n=1),
+                                     P("all_d", n=1)])
+pipe_case("columns", columns_graph, [P(f, inp=i) for i in ("vid", "int") for f in ("w", "k", "all")] + [P("w", n=1, inp="int")])
+FALLBACK_CAP = 1000
+pipe_case("fallback_roots", lambda: roots_graph(K_ROOT_BATCH + 1), [P("all"), P("w"), P("all_d"), P("k", m=1, n=2)], cap=FALLBACK_CAP)
+pipe_case("fallback_converge", lambda: converge_graph(1, 5), [P("all"), P("w")], cap=FALLBACK_CAP)
+
+
+# ---- shaped shards (tests/goshard_worker.py runs them by name, tests/test_gpu_pipe_shards.py checks them)
+PipeShardCase = namedtuple("PipeShardCase", "world counts build queries")
+PIPE_SHARD_CASES = {}
+_pipe_shard_built = {}
+
+
+def pipe_shard_case(name, counts, build):
+    qs = [P(f, n=n) for f in ("all", "w") for n in (2, 3)]
+    PIPE_SHARD_CASES[name] = PipeShardCase(len(counts), list(counts), build, qs)
+
+
+def pipe_shard_built(name):
+    """(Graph, {input name: Interim}, Shards) of a pipe shard case, built once."""
+    if name not in _pipe_shard_built:
+        _pipe_shard_built[name] = PIPE_SHARD_CASES[name].build()
+    return _pipe_shard_built[name]
+
+
+def pipe_shard_cases(world):
+    return [n for n in PIPE_SHARD_CASES if PIPE_SHARD_CASES[n].world == world]
+
+
+def pipe_shard_model(name, k):
+    if ("pipeshard", name, k) not in _models:
+        g, inputs, _ = pipe_shard_built(name)
+        q = PIPE_SHARD_CASES[name].queries[k]
+        plan = pipe_plan(g, q.form, inputs[q.inp], q.over, q.direction, q.m, q.n)
+        _models[("pipeshard", name, k)] = (Model(pipe(g, q.form, inputs[q.inp], q.over, q.direction, q.m, q.n),
+                                                 plan.hop_edges, plan.hop_frontier), plan.walks)
+    return _models[("pipeshard", name, k)]
+
+
+def xchg_roots_bytes(counts, rank):
+    """exchangeRoots' share of lastXchgBytes: a 64-bit root set per row of every peer."""
+    return sum(n * 8 for q, n in enumerate(counts) if q != rank)
+
+
+def _placed(sh, paths, roots):
+    """The graph of (q, i) -> (q, i) edges `paths` over every row of sh (rows without an edge stay vertices), p0 = the
+    edge's number x 9 mod 100 and p1 its number; the input: roots [(q, i)] with 1, 2, 3 input rows in turn."""
+    edges = [edge(sh.vid(*a), sh.vid(*b), 1, 0, (k * 9 % 100, k, 0)) for k, (a, b) in enumerate(paths)]
+    g = Graph(sh.vids(), edges, types=[1])
+    sh.check(g)
+    order = sorted((dup, j) for j in range(len(roots)) for dup in range(1 + j % 3))
+    return g, {"in": pipe_input([input_row(sh.vid(*roots[j]), j, dup) for dup, j in order])}, sh
+
+
+def _w2_pipe():
+    """World 2, counts [5, 70] (the merge's stride is 70, shard 0 has 5 rows). Ten roots on shard 1 reach the hub (0, 0),
+    whose shard holds none of them; X = (1, 60) is reached at hop 1 by a root of its own shard and by one of the peer;
+    (0, 2) -> (0, 3) stays on shard 0. The hub points at rows 20, 21 and 69 (the last) of shard 1."""
+    sh = sharded([5, 70])
+    roots = [(1, i) for i in range(10)] + [(0, 1), (1, 10), (0, 2)]
+    paths = [((1, i), (0, 0)) for i in range(10)] + [((0, 1), (1, 60)), ((1, 10), (1, 60)), ((0, 2), (0, 3)),
+             ((0, 0), (1, 20)), ((0, 0), (1, 21)), ((0, 0), (1, 69)), ((1, 60), (1, 22)), ((1, 60), (0, 4)), ((0, 3), (1, 23)),
+             ((1, 20), (1, 30)), ((1, 21), (1, 31)), ((1, 69), (0, 4)), ((0, 4), (1, 32)), ((1, 22), (1, 33)), ((1, 23), (1, 34))]
+    return _placed(sh, paths, roots)
+
+
+def _w3_empty_pipe():
+    """World 3, counts [3, 0, 66]: shard 1 has no row. Root A = (0, 0) -> (2, 5) -> (0, 1) -> (2, 6): shard 0 scans an edge
+    on hop 1 and none on hop 2 of 3 STEPS. Root B = (2, 0) -> (2, 7) -> (2, 5): row (2, 5) is expanded by hop 2 for A and by
+    hop 3 for B alone (a root set that shard 0 left over from hop 1 would add A's rows to hop 3's).
+    (2, 5) -> (0, 1) and (2, 5) -> (2, 8); (2, 8) -> (2, 9). A third root, the last row of shard 2, walks down its shard."""
+    sh = sharded([3, 0, 66])
+    roots = [(0, 0), (2, 0), (2, 65)]
+    paths = [((0, 0), (2, 5)), ((2, 0), (2, 7)), ((2, 7), (2, 5)), ((2, 5), (0, 1)), ((2, 5), (2, 8)), ((0, 1), (2, 6)),
+             ((2, 8), (2, 9)), ((2, 65), (2, 64)), ((2, 64), (2, 63)), ((2, 63), (2, 62))]
+    return _placed(sh, paths, roots)
+
+
+def _w3_peers_pipe():
+    """World 3, counts [3, 4, 66]: Y = (2, 65) is reached at hop 1 by a root of shard 0 and by a root of shard 1 (its
+    root sets arrive from two peers), and by none of its own shard; Z = (1, 3) by roots of shards 0 and 2."""
+    sh = sharded([3, 4, 66])
+    roots = [(0, 0), (1, 0), (2, 0), (0, 1)]
+    paths = [((0, 0), (2, 65)), ((1, 0), (2, 65)), ((0, 1), (1, 3)), ((2, 0), (1, 3)), ((2, 65), (2, 10)), ((2, 65), (0, 2)),
+             ((1, 3), (2, 11)), ((2, 10), (1, 2)), ((0, 2), (2, 12)), ((2, 11), (2, 13))]
+    return _placed(sh, paths, roots)
+
+
+pipe_shard_case("pipe_w2", [5, 70], _w2_pipe)
+pipe_shard_case("pipe_w3_empty", [3, 0, 66], _w3_empty_pipe)
+pipe_shard_case("pipe_w3_peers", [3, 4, 66], _w3_peers_pipe)

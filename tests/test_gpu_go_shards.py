@@ -48,8 +48,8 @@ def _free_port():
     return p
 
 
-def _launch(tmp, world):
-    names = goref.shard_cases(world)
+def _launch(tmp, world, names=None):
+    names = goref.shard_cases(world) if names is None else names
     port = _free_port()
     env = dict(os.environ, PYTHONPATH=ROOT)
     logs = [open(os.path.join(tmp, f"w{world}r{r}.log"), "w+b") for r in range(world)]
