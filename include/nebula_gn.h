@@ -920,7 +920,9 @@ int32_t ngx_kernel_stats(ngx_ctx* ctx, const ngx_kernel_stat** out, int32_t* n);
  *          stores its rows non-temporally (not kept in L2). Same results.
  * Read-only counters for ngx_get_flag: "jit_compiled", "jit_hits", "jit_failed", "jit_compile_us",
  * "jit_cached", "jit_evicted", "batch_overlaps" (queries of ngx_go_batch that overlapped the next),
- * "dbuf_allocs" / "dbuf_alloc_bytes" (device scratch allocations of the process so far). */
+ * "dbuf_allocs" / "dbuf_alloc_bytes" (device scratch allocations of the process so far), "dbuf_live_bytes"
+ * (device scratch bytes the process holds now, over all its contexts: back where it was once a context
+ * is closed; a block replaced during a pipelined batch counts until the batch's end, when it is freed). */
 int32_t ngx_set_flag(ngx_ctx* ctx, const char* name, int64_t value);
 int32_t ngx_get_flag(ngx_ctx* ctx, const char* name, int64_t* value);
 /* why the last query ran on the interpreter kernels instead of a generated one ("" if it did not) */

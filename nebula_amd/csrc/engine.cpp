@@ -31,60 +31,9 @@
 #include "jit.h"
 #include "kernels.h"
 #include "rowcodec.h"
+#include "engine_ctx.h"
 
 using namespace ngx;
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { throw Error{NGX_E_DEVICE, std::string("HIP: ") + hipGetErrorString(e_) + " at " #x}; } } while (0)
-#define NCCL_OK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) { throw Error{NGX_E_DEVICE, std::string("RCCL: ") + ncclGetErrorString(r_)}; } } while (0)
-
-namespace ngx {
-
-struct DeviceGraph {
-    uint64_t V = 0, vglobal = 0, gbase = 0;
-    std::vector<uint64_t> shardBase;
-    int32_t* vpart = nullptr;
-    int64_t* vid = nullptr;
-    int32_t vidW = 8;                                   // narrowest signed width holding every vid of vid[]
-    VIndex vindex{nullptr, 0};                          // (part, vid) -> row hash index (seed lookup)
-    std::vector<DSlot> slots;
-    // per slot: the row holding CSR position c * kChunk, for every chunk c of the slot (+ a last row): the
-    // chunk map of a final hop over the whole slot (FinalArgs::denseMark)
-    std::vector<const uint64_t*> chunkRow;
-    std::vector<int32_t> mirror;                        // per slot: the slot holding its exact transpose, or -1
-    // per slot with a mirror: the pull hop's head image of the in-lists (kernels.h PullArgs)
-    struct PullHead { const uint32_t* perm = nullptr; const uint32_t* head = nullptr; const uint8_t* nk = nullptr;
-                      uint64_t slices = 0, longRows = 0; };
-    std::vector<PullHead> pullHead;
-    // $$ props across shards: every tag table over ALL global rows (replicas of the other shards'
-    // rows), gathered on the first query that reads a $$ prop, kept until the next commit
-    bool replicas = false;
-    std::vector<HostColumn> repHost;                    // host copies (string bytes back result cells)
-    DTag* rtags = nullptr;
-    DCol* rcols = nullptr;
-    std::vector<DTag> tags;
-    std::vector<DCol> cols;
-    DSlot* dslots = nullptr;
-    DTag* dtags = nullptr;
-    DCol* dcols = nullptr;
-    std::vector<void*> allocs;
-    uint64_t bytes = 0;
-    struct Range { uint64_t dev; const char* host; uint64_t len; };
-    std::vector<Range> strRanges;                       // device string bytes -> host copy
-    ~DeviceGraph() { for (void* p : allocs) (void)hipFree(p); }
-
-    template <typename T>
-    T* upload(const T* src, uint64_t n) {
-        if (n == 0) return nullptr;
-        void* p = nullptr;
-        HIP_OK(hipMalloc(&p, n * sizeof(T)));
-        HIP_OK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-        allocs.push_back(p);
-        bytes += n * sizeof(T);
-        return static_cast<T*>(p);
-    }
-};
-
-}  // namespace ngx
 
 namespace {
 
@@ -102,559 +51,63 @@ constexpr int kPoisonByte = 0xA5;
 // frontier than its earlier queries) would drain the pipeline (r05 trace: the host stalled 560 us on one
 // growth, both final hops behind it running alone). The batch frees them once at its end.
 thread_local bool tDeferFree = false;
-thread_local std::vector<std::pair<void*, bool>> tGraveyard;   // (pointer, page-locked host memory)
-void freeDevice(void* p) {
-    if (!p) return;
-    if (tDeferFree) tGraveyard.emplace_back(p, false);
-    else (void)hipFree(p);
-}
-void freeHost(void* p) {
-    if (!p) return;
-    if (tDeferFree) tGraveyard.emplace_back(p, true);
-    else (void)hipHostFree(p);
+struct Grave { void* p; size_t bytes; bool host; };               // bytes: a DBuf block's share of gDBufLive
+thread_local std::vector<Grave> tGraveyard;
+
+std::atomic<uint64_t> gDBufGen{0};
+std::atomic<uint64_t> gDBufBytes{0};                    // bytes allocated by DBuf growth (flag dbuf_alloc_bytes)
+std::atomic<uint64_t> gDBufLive{0};                     // bytes DBufs hold, parked blocks included (flag dbuf_live_bytes)
+const bool gDBufTrace = std::getenv("NGX_DBUF_TRACE") != nullptr;
+
+void hipFreeCounted(void* p, size_t bytes) {
+    (void)hipFree(p);
+    gDBufLive.fetch_sub(bytes, std::memory_order_relaxed);
 }
 void drainGraveyard() {
-    for (auto& g : tGraveyard) (void)(g.second ? hipHostFree(g.first) : hipFree(g.first));
+    for (auto& g : tGraveyard) {
+        if (g.host) (void)hipHostFree(g.p);
+        else hipFreeCounted(g.p, g.bytes);
+    }
     tGraveyard.clear();
 }
 
-// growable device buffer
-std::atomic<uint64_t> gDBufGen{0};
-std::atomic<uint64_t> gDBufBytes{0};                    // bytes allocated by DBuf growth (flag dbuf_alloc_bytes)
-const bool gDBufTrace = std::getenv("NGX_DBUF_TRACE") != nullptr;
-struct DBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    uint64_t gen = 0;                                   // unique per allocation (hipMalloc may hand back a freed address)
-    template <typename T>
-    T* get(size_t n) {
-        size_t bytes = std::max<size_t>(n * sizeof(T), 64);
-        if (bytes > cap) {
-            const size_t cap0 = cap;
-            freeDevice(p);
-            p = nullptr;
-            size_t c = std::max(bytes, cap * 3 / 2);
-            HIP_OK(hipMalloc(&p, c));
-            cap = c;
-            gen = gDBufGen.fetch_add(1, std::memory_order_relaxed) + 1;
-            gDBufBytes.fetch_add(c, std::memory_order_relaxed);
-            if (gDBufTrace) std::fprintf(stderr, "[ngx dbuf] alloc %zu bytes (asked %zu, had %zu)\n", c, bytes, cap0);
-            if (gPoison.load(std::memory_order_relaxed)) {
-                HIP_OK(hipMemset(p, kPoisonByte, c));
-                HIP_OK(hipDeviceSynchronize());
-            }
-        }
-        return static_cast<T*>(p);
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; gen = 0; }
-};
-
-struct Timer {
-    hipEvent_t a = nullptr, b = nullptr;
-};
-
-// the $$ owner fetch of one lane (fetchDstProps): request lists, exchange blocks, the global row ->
-// fetched-row map, and per record hop of the running query the fetched tag tables (device) with the host
-// copy of their string bytes (result cells read strings back through it)
-struct DstLane {
-    DBuf req, counts, recv, blobS, blobR, rows, map;
-    uint64_t mapRows = 0;
-    std::vector<DBuf> data;                             // per record hop: present / values / strings
-    std::vector<std::string> hostStr;                   // per record hop: its string bytes (host copy)
-    std::vector<const char*> devStr;                    // ... and where they live on the device
-    uint64_t bytes() const {
-        uint64_t b = req.cap + counts.cap + recv.cap + blobS.cap + blobR.cap + rows.cap + map.cap;
-        for (const DBuf& d : data) b += d.cap;
-        return b;
-    }
-    void release() {
-        for (DBuf* b : {&req, &counts, &recv, &blobS, &blobR, &rows, &map}) b->release();
-        for (DBuf& d : data) d.release();
-        data.clear();
-        hostStr.clear();
-        devStr.clear();
-        mapRows = 0;
-    }
-};
-
-// ROCTX range on the host timeline of rocprofv3 (--marker-trace): a query, each hop, each kernel class
-// launch (the reference's FLAGS_trace_go step log, GoExecutor.cpp:559-569). Without a
-// tool attached a push / pop is a check of a registration flag.
-struct RoctxRange {
-    explicit RoctxRange(const char* name) { roctxRangePushA(name); }
-    ~RoctxRange() { roctxRangePop(); }
-    RoctxRange(const RoctxRange&) = delete;
-    RoctxRange& operator=(const RoctxRange&) = delete;
-};
-
 }  // namespace
 
-struct ngx_ctx {
-    int32_t device = 0, rank = 0, world = 1;
-    hipStream_t stream = nullptr;
-    ncclComm_t comm = nullptr;
-    ngx_exchange_fn xchg = nullptr;                    // host collective instead of RCCL (tests)
-    uint64_t* pin = nullptr;                           // host-mapped [value, seq]: scan totals published by
-    uint64_t* pinDev = nullptr;                        // k_scan_tiles (kernels.h Publish)
-    uint64_t pinSeq = 0;                               // words [0, 2): scan totals; [kTailOff ..): query tail
-    static constexpr size_t kPinBytes = 16384;          // up to eight lanes of 256 words (ngx_ctx::Lane)
-    static constexpr size_t kTailOff = 8;               // k_publish_tail: seq, error bits, extra words
-    static constexpr uint32_t kSeedSlot = 80;           // the seed hop's publication (nextPub)
-    static constexpr uint32_t kRowsSlot = 88;           // a record hop's row count (k_final_close)
-    // ngx_go_batch: the next query's host preparation and first hops enqueued while this one's final hop
-    // runs (flag "batch_pipeline"; read-only "batch_overlaps" counts the queries that overlapped)
-    bool batchPipeline = true;
-    struct GoPipe* pipe = nullptr;
-    uint64_t pipeOverlaps = 0;
-    void* xchgUser = nullptr;
-    std::map<int32_t, std::unique_ptr<Space>> spaces;
-    std::string lastError;
-    std::mutex mu;
-    // scratch
-    DBuf visited, F0, F1, estart, ebase, chunkFirst, tileSums, counters, lbStatus, seedPart, seedVid;
-    DBuf cmpStatus[2];                                  // compaction tile / wave totals (kernels.h CompactArgs)
-    DBuf frontierBits;                                  // the pull's frontier bitmap over global rows
-    DBuf oSrc, oDst, oRank, oType, oEntry, progBuf, sendBits, recvBits, vcells, misc, oColDesc, edgeMask;
-    DBuf resvTab, resvCtl;                              // GO final hop: block tables, counters (kargs.h resv*)
-    uint64_t resvTabWords = 0;
-    uint32_t resvSeq = 0, resvLastG = 0, resvLastStride = 0, resvParity = 0;
-    const uint64_t* resvRows = nullptr;                 // this query's last GO final launch's row count (device word)
-    uint64_t strArenaMax = uint64_t(8) << 30;           // bytes of one record hop's result string arena (flag str_arena_max)
-    bool resvClosePending = false;                      // counters handed out, their k_final_close not enqueued
-    DstLane dst;                                        // the $$ owner fetch's buffers (per lane)
-    DBuf oFlags, rowCols, rowLen, rowOff, rowBytes;     // GetNeighbors response rows (encode_rows)
-    DBuf dkTable, dkKeep, dkPre, dSrc, dDst, dRank, dType;   // YIELD DISTINCT (table, marks, compacted rows)
-    std::vector<DBuf> strArena;                         // result string arenas, one per record hop (FinalArgs::strOut)
-    DBuf roots[2], rootBits;                            // multi-root walk: root sets over rows, per-entry bits
-    DBuf rootSend, rootRecv;                            // world > 1: root sets of peer rows, both ways
-    DBuf pwF, pwIn, pwEst, pwCf;                        // ... reading $-: (row, input row) entries, their estart / heads
-    DBuf inX, inLen, inT, inStr, inDesc;                // ... the pipe's input table
-    uint64_t pipeWalks = 0;                             // walks run for FROM $- / $var sentences (flag pipe_walks)
-    // ngx_go_group_by: key table, leaders / flags / group numbers, COUNT_DISTINCT flags, state words, descriptors,
-    // string lengths and their scan, output cells and string bytes, scan tiles
-    DBuf gbTable, gbLeader, gbFlag, gbPre, gbDistinct, gbState, gbDesc, gbSlen, gbSpre, gbCells, gbStr, gbTiles;
-    hipEvent_t gbEv[2] = {nullptr, nullptr};            // ngx_group_result / ngx_order_result.device_ms: made on the first call, kept
-    uint64_t groupByDevice = 0, groupByLds = 0;        // calls completed on the device / through the LDS path
-    int64_t groupLdsMax = -1;                           // flag group_lds_max: -1 by size, else the largest group count
-    uint32_t groupGridMax = 0;                          // flag group_grid_max: most accumulation workgroups, 0: built-in
-    // ngx_go_order_by: row marks, the two tied-row lists, digit counters, state, descriptors, string-length maxima,
-    // winners' rows, their string lengths and scan, output cells and string bytes, scan tiles
-    DBuf obMark, obList[2], obHist, obState, obDesc, obMax, obWin, obSlen, obSpre, obCells, obStr, obTiles;
-    uint64_t orderByDevice = 0;                         // calls completed on the device (flag order_by_device)
-    int64_t orderKMax = 65536;                          // flag order_k_max: the largest offset + count selected on the device
-    uint32_t orderGridMax = 0;                          // flag order_grid_max: most workgroups of a sweep, 0: built-in
-    // paths the selections took so far (OrderState's counters summed; flags order_compactions, ...)
-    uint64_t orderCompactions = 0, orderListCompactions = 0, orderLoopFlushes = 0;
-    // ngx_go_group_order_by: the group rows as columns (values, string lengths) and their descriptors
-    DBuf goCols, goLen, goDesc;
-    uint64_t groupOrderDevice = 0;                      // calls completed on the device (flag group_order_device)
-    // ngx_set_op: row-tuple table, per-slot counts and tickets, the kept rows of either side, state, descriptors,
-    // string lengths and their scan, output cells and string bytes, scan tiles
-    DBuf sbTable, sbCount, sbTaken, sbKeep[2], sbState, sbDesc, sbSlen, sbSpre, sbCells, sbStr, sbTiles;
-    uint64_t setOpDevice = 0;                           // calls completed on the device (flag set_op_device)
-    int64_t setRowsMax = int64_t(1) << 20;              // flag set_rows_max: the most output rows answered on the device
-    uint32_t setGridMax = 0;                            // flag set_grid_max: most workgroups of a sweep, 0: built-in
-    uint64_t setLoopFlushes = 0;                        // SetState::loopFlushes summed (flag set_loop_flushes)
-    // ngx_fetch: per key its vertex row, edge index and hit bits; per 256-key chunk the kept keys and their scan;
-    // the tags seen; yield descriptors; uploaded host keys; string lengths and their scan; output cells and bytes
-    DBuf fxRow, fxEidx, fxHits, fxCount, fxBase, fxTiles, fxSeen, fxDesc, fxKeys[3], fxSlen, fxSpre, fxCells, fxStr;
-    uint64_t fetchDevice = 0;                           // calls completed on the device (flag fetch_device)
-    uint32_t fetchGridMax = 0;                          // flag fetch_grid_max: most workgroups of a sweep, 0: built-in
-    // ngx_lookup: per row its keep byte; per 256-row chunk the kept rows and their scan; the plan's conditions, string
-    // constants and yield descriptors; string lengths and their scan; output cells and bytes
-    DBuf lkKeep, lkCount, lkBase, lkTiles, lkConds, lkPool, lkYs, lkSlen, lkSpre, lkCells, lkStr;
-    uint64_t lookupDevice = 0;                          // calls completed (flag lookup_device)
-    uint32_t lookupGridMax = 0;                         // flag lookup_grid_max: most workgroups of a sweep, 0: built-in
-    int64_t lookupRowsMax = int64_t(1) << 26;           // flag lookup_rows_max: the most output rows
-    // ngx_go_set: the string arenas of the left traversal while the right one runs on the second lane
-    std::vector<DBuf> setArena;
-    // flag set_check_left (debug): ngx_go_set digests the left result before and after the right traversal
-    // (ngx_go_result_digest) and fails the call if they differ; set_left_checks counts the digests that agreed
-    bool setCheckLeft = false;
-    uint64_t setLeftChecks = 0;
-    // ngx_find_path: per side (0 from, 1 to) the incoming / seen bits over rows, the latest level per row (the to side's
-    // with its bits), the rows an expansion reached; per side and level the compacted rows and bits; the sweeps' keep
-    // masks; looked-up seed rows; the path-DAG edges; the state words
-    DBuf fpInc[2], fpSeen[2], fpNew, fpLvl[2], fpTouched[2], fpKeep[3], fpSeed, fpOut, fpState;
-    std::vector<DBuf> fpRows[2], fpMasks[2];
-    int64_t pathRowsMax = int64_t(1) << 20;             // flag path_rows_max: the most path-DAG edges answered on the device
-    uint32_t pathGridMax = 0;                           // flag path_grid_max: most workgroups of a sweep, 0: built-in
-    uint64_t findPathDevice = 0, findPathLevels = 0, findPathEdges = 0, findPathLoopFlushes = 0;
-    DBuf localBits, pullGather;                         // world > 1 pull: this shard's frontier bitmap, all shards' 
-    struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
-    std::vector<ngx_stat> statList;                     // ngx_stats view
-    int64_t maxEdgesPerVertex = INT32_MAX;             // storaged FLAGS_max_edge_returned_per_vertex (GO hops)
-    struct ColBuf { DBuf x, len, t; };
-    struct PinBuf {                                     // page-locked host staging for result D2H
-        void* p = nullptr;
-        size_t cap = 0;
-        char* get(size_t bytes) {
-            if (bytes > cap) {
-                freeHost(p);
-                p = nullptr;
-                // 25 % headroom: result sizes vary from query to query, and re-pinning a GB-sized
-                // staging block costs more than the copy itself
-                size_t c = std::max(bytes + bytes / 4, cap * 3 / 2);
-                // coherent (fine-grained): kernels read the seeds / inputs the host just wrote, and the copy
-                // kernel stores results the host reads after the stream synchronises; neither may meet a
-                // stale line the GPU kept cached from an earlier query (hipHostMallocDefault is non-coherent)
-                HIP_OK(hipHostMalloc(&p, c, hipHostMallocMapped | hipHostMallocCoherent));
-                cap = c;
-            }
-            return static_cast<char*>(p);
-        }
-        // grow keeping the first `keep` bytes (the caller has synchronised with copies out of the old block)
-        char* getKeep(size_t bytes, size_t keep) {
-            if (bytes <= cap) return static_cast<char*>(p);
-            std::vector<char> save(static_cast<char*>(p), static_cast<char*>(p) + std::min(keep, cap));
-            char* n = get(bytes);
-            std::memcpy(n, save.data(), save.size());
-            return n;
-        }
-        void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    } hostStage, inStage, seedStage;
-    std::string progLast;                               // the bytes of the last program upload ...
-    const char* progLastPtr = nullptr;                  // ... and where they went (uploadPrograms skips a repeat)
-    std::string progImg;                                // this call's program bytes (compared before staging)
-    std::vector<ColBuf> oCols;                          // result columns (columnar, HBM)
-    std::vector<ColBuf> dCols;                          // DISTINCT: the other half of each column's double buffer
-    std::vector<OutCol> oColView;                       // their device pointers, as uploaded to oColDesc
-    uint64_t visitedSize = 0;
-    uint8_t epoch = 0;
-    // pull expansion (kernels.h launchPull): segment queue + its counters, kept zero between launches
-    DBuf pullSeg, pullCtl;
-    uint64_t pullSegWords = 0;
-    int32_t compactLaneRows = 0;                        // compaction rows per lane: 0 = by shard size, else 4 / 8 / 16
-    int32_t compactWg = 0;                              // compaction workgroup threads: 0 = auto, 256 or 1024
-    // generated GO final hops store result rows / load columns non-temporally (flags final_nt_stores /
-    // final_nt_loads). r06, both on: the batch 0.2796 vs 0.2833 ms/step on one box (8 rounds), 0.2898 vs
-    // 0.2901 on another (6); the final hop alone ~1% slower; either alone slower than neither. Kept off.
-    bool finalNtStores = false;
-    bool finalNtLoads = false;
-    uint32_t resvGroups = kResvGroups;                  // GO final hop row-reservation groups (flag resv_groups, 1 .. kResvMaxGroups)
-    int64_t pullFactor = 200;                           // pull when 100 x hop edges >= pullFactor x shard rows (0: never)
-    uint64_t pullHops = 0;
-    // sparse intermediate hops (kernels.h SparseArgs): a push hop with E * sparseFactor <= V builds the next
-    // frontier in the expansion itself (flag "sparse_factor", 0 = never, < 0 = every push hop; read-only
-    // "sparse_hops")
-    int64_t sparseFactor = 16;
-    uint64_t sparseHops = 0;
-    bool pullPredict = false;                           // hop 2 of the last query pulled (world 1): launch it early
-    DBuf sparseCtl;                                     // the sparse kernel's counters, kept zero between launches
-    DBuf estart2, ebase2, chunkFirst2;                  // the next hop's entry arrays while the sparse kernel reads this hop's
-    // world > 1 push hops: frontier exchanged as vid lists instead of bitmaps (flag "xchg_lists": -1 by the
-    // hop's size, 0 bitmaps, 1 lists; read-only "xchg_list_hops")
-    int64_t xchgLists = -1;
-    uint64_t xchgListHops = 0;
-    DBuf xListSend, xListRecv, xCounts;
-    // the frontier bitmap is known to be all zero (a sparse hop's dedup set starts from it): set by a
-    // compaction that wrote zeros, cleared by every other writer. Keyed on the allocation (pointer and
-    // DBuf::gen) and the words zeroed: a query in a space with more rows needs more zero words
-    bool bitsClean = false;
-    const void* bitsCleanPtr = nullptr;
-    uint64_t bitsCleanGen = 0, bitsCleanWords = 0;
-    // device-driven hops (no host round trip per hop). Off by default: on MI355X the upper-bound grids
-    // and the idle launch of the expansion not taken cost what the round trips saved (C2 step: device
-    // 680 vs 656 us, profiles/r02_dyn_*); kept as an option ("dyn_hops", NGX_DYN_HOPS=1)
-    bool dynHops = false;
-    bool deviceLibm = false;                            // inexact libm of row values on the device (exprc.cpp)
-    bool reservoirSampling = false;                     // storaged FLAGS_enable_reservoir_sampling: refused
-    bool narrowColumns = true;                          // integer columns at their narrowest width (at commit)
-    bool traceGo = false;                               // graphd FLAGS_trace_go: per-step log on stderr
-    DBuf dynStats;                                      // per hop: packed (|F|, E) written by seed / compaction
-    int cus = 256;                                      // compute units of the device
-    // RCCL watchdog: collective work must finish within this; else the communicator is aborted
-    int64_t rcclTimeoutMs = 120000;
-    bool broken = false;                                // communicator aborted: every later call fails
-    uint64_t lastXchgBytes = 0;                         // bytes this shard sent in the last exchange
-    // per-query kernels (hipRTC)
-    bool jitOn = true;
-    JitCache jit;
-    std::string jitNote;
-    // profiling
-    bool prof = false;
-    struct Stat { std::string name; uint32_t launches = 0; double ms = 0; uint64_t bytes = 0; };
-    std::vector<Stat> stats;
-    std::vector<ngx_kernel_stat> statView;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
-    std::vector<hipEvent_t> eventPool;
-    size_t eventNext = 0;
+void ngx::freeDevice(void* p, size_t bytes) {
+    if (!p) return;
+    if (tDeferFree) tGraveyard.push_back({p, bytes, false});
+    else hipFreeCounted(p, bytes);
+}
+void ngx::freeHost(void* p) {
+    if (!p) return;
+    if (tDeferFree) tGraveyard.push_back({p, 0, true});
+    else (void)hipHostFree(p);
+}
 
-    // A query lane: the per-query scratch of the hop loop and its publication slots (words [pinLane,
-    // pinLane + kLaneWords) of the host-mapped block). ngx_go_batch runs consecutive queries on rotating
-    // lanes, so that one query's hops run on the device beside the earlier queries' final hops (GoPipe).
-    // The active lane's fields are the members above; lane k's are parked in parked[k] while it is not
-    // active (parked[activeLane] holds an empty set); useLane swaps sets.
-    uint32_t pinLane = 0;
-    static constexpr uint32_t kLaneWords = 256;
-    static constexpr int kMaxLanes = 8;                 // kPinBytes / (8 * kLaneWords)
-    struct Lane {
-        DBuf visited, F0, F1, estart, ebase, chunkFirst, estart2, ebase2, chunkFirst2, tileSums, counters, lbStatus,
-            seedPart, seedVid, cmpStatus[2], frontierBits, localBits, edgeMask, pullSeg, pullCtl, sparseCtl, dynStats, progBuf;
-        uint64_t visitedSize = 0, pullSegWords = 0;
-        uint8_t epoch = 0;
-        bool bitsClean = false;
-        const void* bitsCleanPtr = nullptr;
-        uint64_t bitsCleanGen = 0, bitsCleanWords = 0;
-        std::string progLast;
-        const char* progLastPtr = nullptr;
-        PinBuf inStage, seedStage;
-        uint32_t pinLane = 0;
-        // the lane's result rows and their reservation state (a query's final hop writes its lane's arrays,
-        // so its k_final_close may run beside the next query's final hop)
-        DBuf oSrc, oDst, oRank, oType, oColDesc, resvTab, resvCtl;
-        std::vector<ColBuf> oCols;
-        std::vector<OutCol> oColView;
-        uint64_t resvTabWords = 0;
-        uint32_t resvLastG = 0, resvLastStride = 0, resvParity = 0;
-        bool resvClosePending = false;
-        DstLane dst;
-    } parked[kMaxLanes];
-    int activeLane = 0;
-    // lanes of a pipelined batch (flag "batch_lanes", 2 .. kMaxLanes): up to lanes - 1 queries wait at their
-    // deferral point while the next one runs its hops
-    int32_t batchLanes = 4;                            // r06, two final streams: 4 lanes 0.299 vs 3 lanes 0.303 ms per step
-    // ngx_go_batch's streams (GoPipe, created with the context at world 1): the queries' hops on the front
-    // stream, the last final hop of each overlapped query on the final stream; finalStream is set while a
-    // pipelined batch runs. The coroutine stacks of the batch's queries (one per lane).
-    // [0] front (hops), [1] final (final hops), [2] the second front stream (flag batch_fronts 2: consecutive
-    // queries' hops on alternate front streams, so two queries' hop chains run at once beside a final hop)
-    // or the close stream (k_final_close of an overlapped final hop beside the next query's final hop: the
-    // close reads and moves its own lane's rows only)
-    hipStream_t pipeStreams[4] = {nullptr, nullptr, nullptr, nullptr};   // + [3] the close stream
-    hipEvent_t pipeEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // a ring of events for the batch's cross-stream waits: each wait gets an event no later record re-arms
-    // while the wait may be pending (flag batch_event_ring; 0: the fixed pipeEv per role)
-    static constexpr int kPipeRing = 64;
-    hipEvent_t pipeRing[kPipeRing] = {};
-    uint32_t pipeRingNext = 0;
-    bool batchEventRing = true;
-    hipEvent_t pipeEvent(int role) {
-        if (!batchEventRing || !pipeRing[0]) return pipeEv[role];
-        return pipeRing[pipeRingNext++ % kPipeRing];
+void DBuf::grow(size_t bytes) {
+    const size_t cap0 = cap;
+    freeDevice(p, cap);
+    p = nullptr;
+    cap = 0;
+    size_t c = std::max(bytes, cap0 * 3 / 2);
+    HIP_OK(hipMalloc(&p, c));
+    cap = c;
+    gen = gDBufGen.fetch_add(1, std::memory_order_relaxed) + 1;
+    gDBufBytes.fetch_add(c, std::memory_order_relaxed);
+    gDBufLive.fetch_add(c, std::memory_order_relaxed);
+    if (gDBufTrace) std::fprintf(stderr, "[ngx dbuf] alloc %zu bytes (asked %zu, had %zu)\n", c, bytes, cap0);
+    if (gPoison.load(std::memory_order_relaxed)) {
+        HIP_OK(hipMemset(p, kPoisonByte, c));
+        HIP_OK(hipDeviceSynchronize());
     }
-    // set while a pipelined batch runs with flag batch_close_stream (default on since the second front
-    // stream: C2 0.310 vs 0.317 ms per step; with one front stream it measured 0.330 vs 0.324, the next final
-    // hop waiting for its front-stream dependency anyway)
-    hipStream_t closeStream = nullptr;
-    bool batchCloseStream = true;
-    int32_t batchFronts = 2;                           // front streams of a pipelined batch (1 or 2)
-    // flag batch_cu_split N > 0: the batch's front streams on N CUs (every CU i with (i / 8) % (256 / N / 8)
-    // == 0, spread over the XCDs), its final stream on the others, so the hops' waves do not take slots
-    // from the final hop (streams created on first use with that split)
-    int32_t batchCuSplit = 0, cuSplitMade = 0;
-    hipStream_t splitStreams[4] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t pipeFronts = 1;                            // ... of the batch that runs
-    hipStream_t finalStream = nullptr;
-    // flag batch_finals 2: consecutive queries' final hops on two final streams (the close after its final
-    // hop on the same stream, no close stream), so one final hop starts while the other drains its tail;
-    // finalCur is the running query's
-    int32_t batchFinals = 2;
-    // per lane: the event after its last overlapped final hop's close. The lane's next final hop waits for it:
-    // that close still moves the earlier query's rows inside the lane's result arrays and reads its block
-    // table after the earlier query has read its row count (published by the close's first workgroup), and
-    // with two final streams nothing else orders the two (r06: a C2 batch at 4 groups failed on it)
-    hipEvent_t laneCloseEv[kMaxLanes] = {};
-    bool laneClosePending[kMaxLanes] = {};                           // C2: 0.302 vs 0.309 ms per step (tools/ab_batch.py, 10 rounds)
-    hipStream_t finalStream2 = nullptr, finalCur = nullptr;
-    void* coStack[kMaxLanes] = {};
-    static constexpr size_t kCoStackBytes = size_t(16) << 20;   // + a guard page below each
-    void swapLane(Lane& L) {
-#define NGX_LANE_SWAP(f) std::swap(f, L.f);
-        NGX_LANE_SWAP(visited) NGX_LANE_SWAP(F0) NGX_LANE_SWAP(F1) NGX_LANE_SWAP(estart)
-        NGX_LANE_SWAP(ebase) NGX_LANE_SWAP(chunkFirst) NGX_LANE_SWAP(estart2) NGX_LANE_SWAP(ebase2) NGX_LANE_SWAP(chunkFirst2)
-        NGX_LANE_SWAP(tileSums) NGX_LANE_SWAP(counters) NGX_LANE_SWAP(lbStatus) NGX_LANE_SWAP(seedPart) NGX_LANE_SWAP(seedVid)
-        NGX_LANE_SWAP(cmpStatus[0]) NGX_LANE_SWAP(cmpStatus[1]) NGX_LANE_SWAP(frontierBits) NGX_LANE_SWAP(localBits)
-        NGX_LANE_SWAP(edgeMask) NGX_LANE_SWAP(pullSeg) NGX_LANE_SWAP(pullCtl) NGX_LANE_SWAP(sparseCtl) NGX_LANE_SWAP(dynStats)
-        NGX_LANE_SWAP(progBuf) NGX_LANE_SWAP(visitedSize) NGX_LANE_SWAP(pullSegWords) NGX_LANE_SWAP(epoch)
-        NGX_LANE_SWAP(bitsClean) NGX_LANE_SWAP(bitsCleanPtr) NGX_LANE_SWAP(bitsCleanGen) NGX_LANE_SWAP(bitsCleanWords) NGX_LANE_SWAP(progLast) NGX_LANE_SWAP(progLastPtr)
-        NGX_LANE_SWAP(inStage) NGX_LANE_SWAP(seedStage) NGX_LANE_SWAP(pinLane)
-        NGX_LANE_SWAP(oSrc) NGX_LANE_SWAP(oDst) NGX_LANE_SWAP(oRank) NGX_LANE_SWAP(oType) NGX_LANE_SWAP(oColDesc)
-        NGX_LANE_SWAP(resvTab) NGX_LANE_SWAP(resvCtl) NGX_LANE_SWAP(oCols) NGX_LANE_SWAP(oColView)
-        NGX_LANE_SWAP(resvTabWords) NGX_LANE_SWAP(resvLastG) NGX_LANE_SWAP(resvLastStride) NGX_LANE_SWAP(resvParity)
-        NGX_LANE_SWAP(resvClosePending) NGX_LANE_SWAP(dst)
-#undef NGX_LANE_SWAP
-    }
-    void initLanes() {
-        for (int k = 1; k < kMaxLanes; k++) parked[k].pinLane = k * kLaneWords;
-    }
-    void useLane(int k) {
-        if (k == activeLane) return;
-        swapLane(parked[activeLane]);                  // park the active lane (the empty set comes in) ...
-        swapLane(parked[k]);                           // ... and bring lane k in (the empty set goes to its slot)
-        activeLane = k;
-    }
-
-    void releaseLane() {
-        for (DBuf* b : {&visited, &F0, &F1, &estart, &ebase, &chunkFirst, &estart2, &ebase2, &chunkFirst2, &tileSums, &counters,
-                        &lbStatus, &seedPart, &seedVid, &cmpStatus[0], &cmpStatus[1], &frontierBits, &localBits, &edgeMask,
-                        &pullSeg, &pullCtl, &sparseCtl, &dynStats, &progBuf, &oSrc, &oDst, &oRank, &oType, &oColDesc,
-                        &resvTab, &resvCtl}) b->release();
-        for (auto& cb : oCols) { cb.x.release(); cb.len.release(); cb.t.release(); }
-        inStage.release();
-        seedStage.release();
-        dst.release();
-    }
-    // the parked lanes' scratch and result rows freed (flag batch_release_lanes, or release_lanes = 1 once):
-    // a pipelined batch leaves lanes 1 .. kMaxLanes - 1 holding buffers as large as lane 0's. Called with no
-    // batch running; hipFree waits for the work that still reads them.
-    uint64_t releaseParked() {
-        uint64_t freed = 0;
-        const int was = activeLane;
-        for (int k = 0; k < kMaxLanes; k++) {
-            if (k == was) continue;
-            useLane(k);
-            for (DBuf* b : {&visited, &F0, &F1, &estart, &ebase, &chunkFirst, &estart2, &ebase2, &chunkFirst2, &tileSums,
-                            &counters, &lbStatus, &seedPart, &seedVid, &cmpStatus[0], &cmpStatus[1], &frontierBits,
-                            &localBits, &edgeMask, &pullSeg, &pullCtl, &sparseCtl, &dynStats, &progBuf, &oSrc, &oDst, &oRank,
-                            &oType, &oColDesc, &resvTab, &resvCtl})
-                freed += b->cap;
-            for (auto& cb : oCols) freed += cb.x.cap + cb.len.cap + cb.t.cap;
-            freed += dst.bytes();
-            releaseLane();
-            oCols.clear();
-            oColView.clear();
-            visitedSize = pullSegWords = 0;
-            epoch = 0;
-            bitsClean = false;
-            bitsCleanPtr = nullptr;
-            bitsCleanGen = bitsCleanWords = 0;
-            progLast.clear();
-            progLastPtr = nullptr;
-            resvTabWords = 0;
-            resvLastG = resvLastStride = resvParity = 0;
-            resvClosePending = false;
-        }
-        useLane(was);
-        return freed;
-    }
-    uint64_t releasedBytes = 0;
-    bool batchReleaseLanes = false;
-    // $$ props at world > 1 (flag dst_props): -1 by size (replicas while every shard's tag data fits
-    // dstReplicaMax bytes), 0 replicas of every tag table over the global rows (gathered once per snapshot),
-    // 1 the owner fetch per record hop (GoExecutor::fetchVertexProps -> QueryVertexPropsProcessor)
-    int32_t dstProps = -1;
-    // the final hop over every CSR position of its slot, reading the frontier from the marks (no next-frontier
-    // list, no entry arrays): after a pulled hop at world 1 with one OVER type (flag dense_final)
-    bool denseFinal = true;
-    bool denseCloseTotal = true;                        // its frontier total summed by the close (flag dense_close_total)
-    bool denseWorldDev = true;                          // world > 1: its totals kept on the device (flag dense_world_dev)
-    uint64_t denseFinals = 0;
-    // a dense final hop of an eligible generated kernel (jit.h jitDenseEligible) issues its edge-column loads
-    // ahead of the frontier bits (final_kernels.h finalBodyDense; flag dense_early_loads); 0: the generic body
-    bool denseEarlyLoads = true;
-    uint64_t denseEarlyFinals = 0;                      // launches that took it (flag dense_early_finals, read-only)
-    uint64_t dstReplicaMax = uint64_t(1) << 30;
-    uint64_t dstFetches = 0, dstFetchRows = 0;
-    ~ngx_ctx() {                                       // also the cleanup of ngx_open's error paths
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (auto st : pipeStreams) if (st) (void)hipStreamSynchronize(st);
-        for (auto st : splitStreams) if (st) (void)hipStreamSynchronize(st);
-        spaces.clear();
-        for (DBuf* b : {&oEntry, &sendBits, &recvBits,
-                        &vcells, &misc, &oFlags, &rowCols, &rowLen, &rowOff, &rowBytes, &dkTable, &dkKeep, &dkPre, &dSrc, &dDst,
-                        &dRank, &dType, &xListSend, &xListRecv, &xCounts, &gbTable, &gbLeader, &gbFlag, &gbPre, &gbDistinct,
-                        &gbState, &gbDesc, &gbSlen, &gbSpre, &gbCells, &gbStr, &gbTiles, &obMark, &obList[0], &obList[1],
-                        &obHist, &obState, &obDesc, &obMax, &obWin, &obSlen, &obSpre, &obCells, &obStr, &obTiles, &sbTable, &sbCount,
-                        &sbTaken, &sbKeep[0], &sbKeep[1], &sbState, &sbDesc, &sbSlen, &sbSpre, &sbCells, &sbStr, &sbTiles}) b->release();
-        for (DBuf& b : setArena) b.release();
-        for (DBuf* b : {&fpInc[0], &fpInc[1], &fpSeen[0], &fpSeen[1], &fpNew, &fpLvl[0], &fpLvl[1], &fpTouched[0], &fpTouched[1],
-                        &fpKeep[0], &fpKeep[1], &fpKeep[2], &fpSeed, &fpOut, &fpState}) b->release();
-        for (auto* v : {&fpRows[0], &fpRows[1], &fpMasks[0], &fpMasks[1]})
-            for (DBuf& b : *v) b.release();
-        for (auto& cb : dCols) { cb.x.release(); cb.len.release(); cb.t.release(); }
-        hostStage.release();
-        for (auto e : eventPool) (void)hipEventDestroy(e);
-        for (auto e : gbEv) if (e) (void)hipEventDestroy(e);
-        for (auto e : pipeEv) if (e) (void)hipEventDestroy(e);
-        for (auto e : laneCloseEv) if (e) (void)hipEventDestroy(e);
-        for (auto e : pipeRing) if (e) (void)hipEventDestroy(e);
-        for (auto st : pipeStreams) if (st) (void)hipStreamDestroy(st);
-        for (auto st : splitStreams) if (st) (void)hipStreamDestroy(st);
-        for (void* st : coStack) if (st) munmap(st, kCoStackBytes + 4096);
-        if (comm) (void)ncclCommDestroy(comm);
-        if (pin) (void)hipHostFree(pin);
-        releaseLane();
-        for (auto& L : parked) {
-            swapLane(L);
-            releaseLane();
-        }
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    hipEvent_t ev() {
-        if (eventNext == eventPool.size()) {
-            hipEvent_t e;
-            HIP_OK(hipEventCreate(&e));
-            eventPool.push_back(e);
-        }
-        return eventPool[eventNext++];
-    }
-    int statIndex(const char* name) {
-        for (size_t i = 0; i < stats.size(); i++) if (stats[i].name == name) return static_cast<int>(i);
-        stats.push_back(Stat{name});
-        return static_cast<int>(stats.size()) - 1;
-    }
-    // host timeline of a query (NGX_HOST_TRACE=1): launches and publication waits, printed per query
-    bool htrace = false;
-    // pipelined batch host timeline (NGX_PIPE_TRACE=1): the same marks, tagged with the running query and
-    // kept with absolute CLOCK_MONOTONIC times until the batch ends (the pipeline stays on)
-    bool ptrace = false;
-    int32_t ptraceQuery = -1;
-    std::vector<std::pair<std::string, int64_t>> pmarks;
-    void pmark(const std::string& what) {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        pmarks.emplace_back("q" + std::to_string(ptraceQuery) + " " + what,
-                            static_cast<int64_t>(ts.tv_sec) * 1000000000LL + ts.tv_nsec);
-    }
-    std::vector<std::pair<std::string, std::chrono::steady_clock::time_point>> hmarks;
-    void hmark(const std::string& what) {
-        if (htrace) hmarks.emplace_back(what, std::chrono::steady_clock::now());
-        if (ptrace) pmark(what);
-    }
-    void hflush() {
-        if (!htrace || hmarks.empty()) return;
-        std::string line = "[ngx host]";
-        for (auto& m : hmarks)
-            line += " " + m.first + "@" + std::to_string(std::chrono::duration<double, std::micro>(m.second - hmarks[0].second).count()).substr(0, 7);
-        std::fprintf(stderr, "%s\n", line.c_str());
-        hmarks.clear();
-    }
-    // bracket a launch group with events when profiling
-    template <typename F>
-    void timed(const char* name, uint64_t algoBytes, F&& f) {
-        RoctxRange range(name);                        // a ROCTX range per kernel class launch (rocprofv3 --marker-trace)
-        if (htrace || ptrace) hmark(std::string("L:") + name);
-        if (!prof) { f(); if (htrace || ptrace) hmark(std::string("l:") + name); return; }
-        int k = statIndex(name);
-        hipEvent_t a = ev(), b = ev();
-        HIP_OK(hipEventRecord(a, stream));
-        f();
-        HIP_OK(hipEventRecord(b, stream));
-        pending.push_back({k, {a, b}});
-        stats[k].launches++;
-        stats[k].bytes += algoBytes;
-    }
-    void addBytes(const char* name, uint64_t b) {
-        if (prof) stats[statIndex(name)].bytes += b;
-    }
-    void collectTimings() {
-        if (!prof) return;
-        for (auto& p : pending) {
-            HIP_OK(hipEventSynchronize(p.second.second));
-            float ms = 0;
-            HIP_OK(hipEventElapsedTime(&ms, p.second.first, p.second.second));
-            stats[p.first].ms += ms;
-        }
-        pending.clear();
-        eventNext = 0;
-    }
-};
+}
+void DBuf::release() {
+    if (p) hipFreeCounted(p, cap);
+    p = nullptr, cap = 0, gen = 0;
+}
 
 // ngx_go_batch's pipeline. The batch's queries run as coroutines (ucontext) on the calling thread, one
-// at a time, each on a stack of its own, consecutive queries on alternate lanes (ngx_ctx::Lane: scratch
+// at a time, each on a stack of its own, consecutive queries on alternate lanes (LaneState: scratch
 // and publication slots). A query's hops run on the front stream and its last final hop (with its close)
 // on the final stream, each stream on its own share of the CUs. A query whose final hop is enqueued
 // yields before it waits for its row count (it is "deferred"); the next query then runs its hops on its
@@ -682,16 +135,6 @@ struct GoPipe {
 };
 
 namespace {
-
-int32_t fail(ngx_ctx* c, int32_t code, const std::string& msg) {
-    c->lastError = msg;
-    return code;
-}
-
-Space* findSpace(ngx_ctx* c, int32_t id) {
-    auto it = c->spaces.find(id);
-    return it == c->spaces.end() ? nullptr : it->second.get();
-}
 
 // ------------------------------------------------------------------------ upload
 // Integer columns can be stored at the narrowest signed width that holds every value (HBM bytes per
@@ -748,10 +191,12 @@ void uploadColumns(DeviceGraph& d, std::vector<HostColumn>& hc, uint64_t n, bool
     }
 }
 
+}  // namespace
+
 // TTL info of a schema (buildTTLInfoAndRespSchema, QueryBaseProcessor.inl:670-797): present when
 // ttl_col is set and ttl_duration > 0 (rows are then read, bad rows skipped); the column is checked
 // only when the latest schema types it INT / TIMESTAMP / VID (checkDataExpiredForTTL), else -1
-bool ttlInfo(const SchemaSet* ss, int32_t& col, int64_t& dur) {
+bool ngx::ttlInfo(const SchemaSet* ss, int32_t& col, int64_t& dur) {
     col = -1;
     dur = 0;
     if (!ss) return false;
@@ -762,6 +207,8 @@ bool ttlInfo(const SchemaSet* ss, int32_t& col, int64_t& dur) {
     dur = l.ttlDur;
     return true;
 }
+
+namespace {
 
 std::unique_ptr<DeviceGraph> upload(HostGraph& g, const Space& sp) {
     auto d = std::make_unique<DeviceGraph>();
@@ -922,10 +369,12 @@ uint64_t maxMultiplicity(const std::vector<int64_t>& v) {
     return best;
 }
 
+}  // namespace
+
 // seeds (vids then parts) into one device block with one copy; dvid holds n * 12 bytes. The seeds
 // have their own page-locked stage: the seed hop is launched before the programs are staged
 // (runGo), so the two must not share a block that may move when it grows.
-void stageSeeds(ngx_ctx* c, const std::vector<int32_t>& parts, const std::vector<int64_t>& vids, int32_t* dpart,
+void ngx::stageSeeds(ngx_ctx* c, const std::vector<int32_t>& parts, const std::vector<int64_t>& vids, int32_t* dpart,
                 int64_t* dvid) {
     const size_t n = vids.size();
     char* hp = c->seedStage.get(n * 12 + 64);             // the previous call has synchronised with its copies
@@ -938,6 +387,8 @@ void stageSeeds(ngx_ctx* c, const std::vector<int32_t>& parts, const std::vector
         HIP_OK(hipMemcpyAsync(dpart, hp + n * 8, n * 4, hipMemcpyHostToDevice, c->stream));
     }
 }
+
+namespace {
 
 // seeds (vids then parts) into the page-locked seed stage, returned as device-visible pointers into it
 // (mapped): the seed kernel reads them over the bus, no copy launch. False when the stage cannot be
@@ -1284,14 +735,6 @@ void ensureVisited(ngx_ctx* c, uint64_t n) {
     }
 }
 
-template <typename T>
-T readScalar(ngx_ctx* c, const T* dev) {
-    T v;
-    HIP_OK(hipMemcpyAsync(&v, dev, sizeof(T), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    return v;
-}
-
 // next publication slot for a scan total (none when the mapped buffer is unavailable)
 // slot 0 (words 0..3) for every publication but the seed hop's, which has slot kSeedSlot of its own: a
 // hop sized on the device publishes while the seed total is still unread (spec1)
@@ -1473,7 +916,9 @@ struct GnResultHolder {
     std::vector<ngx_schema_def> schemaView;
 };
 
-HopSlots makeHopSlots(const Space& sp, const DeviceGraph& d, const std::vector<int32_t>& types,
+}  // namespace
+
+HopSlots ngx::makeHopSlots(const Space& sp, const DeviceGraph& d, const std::vector<int32_t>& types,
                       std::vector<int32_t>& hopTypes) {
     HopSlots hs{};
     hs.n = 0;
@@ -1499,6 +944,8 @@ HopSlots makeHopSlots(const Space& sp, const DeviceGraph& d, const std::vector<i
     }
     return hs;
 }
+
+namespace {
 
 // host collective (ngx_config.exchange): device blocks staged through host memory
 void hostExchange(ngx_ctx* c, int32_t op, const void* dsend, void* drecv, uint64_t bytes) {
@@ -2047,15 +1494,16 @@ int32_t ngx_synchronize(ngx_ctx* c) {
     return NGX_OK;
 }
 
-static int32_t resultDigest(ngx_ctx* c, const ngx_go_result* r, uint64_t out[3]);
 int32_t ngx_go_result_digest(ngx_ctx* c, const ngx_go_result* r, uint64_t out[3]) {
     if (!c || !r || !out) return NGX_E_BAD_ARGUMENT;
     std::lock_guard<std::mutex> g(c->mu);
     return resultDigest(c, r, out);
 }
 
+}  // extern "C"
+
 // ngx_go_result_digest under the caller's lock
-static int32_t resultDigest(ngx_ctx* c, const ngx_go_result* r, uint64_t out[3]) {
+int32_t ngx::resultDigest(ngx_ctx* c, const ngx_go_result* r, uint64_t out[3]) {
     try {
         HIP_OK(hipSetDevice(c->device));
         if (r->code != NGX_OK || (r->nrows && !r->dev_cols && r->ncols)) return fail(c, NGX_E_BAD_ARGUMENT, "digest: not a device-resident result");
@@ -2085,6 +1533,8 @@ static int32_t resultDigest(ngx_ctx* c, const ngx_go_result* r, uint64_t out[3])
     }
     return NGX_OK;
 }
+
+extern "C" {
 
 int32_t ngx_set_profiling(ngx_ctx* c, int32_t on) {
     std::lock_guard<std::mutex> g(c->mu);
@@ -2258,6 +1708,7 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "batch_finals") *value = c->batchFinals;
     else if (n == "dbuf_allocs") *value = static_cast<int64_t>(gDBufGen.load());
     else if (n == "dbuf_alloc_bytes") *value = static_cast<int64_t>(gDBufBytes.load());
+    else if (n == "dbuf_live_bytes") *value = static_cast<int64_t>(gDBufLive.load());
     else if (n == "dst_props") *value = c->dstProps;
     else if (n == "dense_final") *value = c->denseFinal ? 1 : 0;
     else if (n == "dense_close_total") *value = c->denseCloseTotal ? 1 : 0;
@@ -2974,7 +2425,7 @@ void growKeep(ngx_ctx* c, DBuf& b, size_t bytes, size_t keep) {
     HIP_OK(hipMemcpyAsync(nb.p, b.p, keep, hipMemcpyDeviceToDevice, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     b.release();
-    b = nb;
+    b = std::move(nb);
 }
 
 // the final kernel's look-back words: ticket / row counter, one status per chunk, the done counter
@@ -4951,10 +4402,8 @@ int32_t runPipe(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R) 
 
 }  // namespace
 
-namespace {
-
 // ngx_go under the caller's lock of c->mu
-int32_t goCall(ngx_ctx* c, const ngx_go_plan* p, ngx_go_result** out) {
+int32_t ngx::goCall(ngx_ctx* c, const ngx_go_plan* p, ngx_go_result** out) {
     auto R = std::make_unique<GoResultHolder>();
     R->tIn = std::chrono::steady_clock::now();
     R->tLaunch = R->tDone = R->tIn;
@@ -5004,6 +4453,8 @@ int32_t goCall(ngx_ctx* c, const ngx_go_plan* p, ngx_go_result** out) {
     *out = &R.release()->r;
     return rc;
 }
+
+namespace {
 
 // one query of a batch: exactly one ngx_go, its counts (and digest) kept, its result freed at once
 void batchQuery(ngx_ctx* c, const ngx_go_plan* p, GoJob& j, bool digest) {
@@ -5825,1850 +5276,3 @@ extern "C" int32_t ngx_stats(ngx_ctx* c, const ngx_stat** out, int32_t* n) {
     return NGX_OK;
 }
 
-// ============================================================================ GROUP BY
-namespace {
-
-struct GroupResultHolder {
-    ngx_group_result r{};
-    std::vector<int32_t> colTypes;
-    std::vector<ngx_cell> cells;
-    std::string strings;
-};
-static_assert(sizeof(GroupCell) == sizeof(ngx_cell) && offsetof(GroupCell, v) == offsetof(ngx_cell, v), "GroupCell is ngx_cell");
-
-bool intLike(int32_t t) { return t == NGX_T_INT || t == NGX_T_VID || t == NGX_T_TIMESTAMP; }
-
-// The grouping up to its state words, shared by ngx_go_group_by (which emits cells from it) and
-// ngx_go_group_order_by (which turns it into columns): groupPrepare checks the plan and lays out columns, state
-// slots and yield descriptors on the host; groupAccumulate runs assign + scan + accumulate and leaves the
-// device state in the context's gb* buffers.
-struct GroupStage {
-    uint64_t n = 0, ngroups = 0;
-    std::vector<GroupCol> cols;                                   // the result columns the kernels read
-    std::vector<int32_t> typeOf, keyIdx, distinctCol;             // distinctCol: value column of each COUNT_DISTINCT pass
-    std::vector<GroupSlot> slots;
-    std::vector<GroupEmit> emit;
-    std::vector<uint8_t> isCount;                                 // per yield: a COUNT / COUNT_DISTINCT state word, in [0, n]
-    GroupCol* colsDev = nullptr;
-    GroupSlot* slotsDev = nullptr;
-    GroupEmit* emitDev = nullptr;
-    uint32_t* leader = nullptr;
-    uint64_t* flag = nullptr;
-    uint64_t* pre = nullptr;
-    uint64_t* tiles = nullptr;
-    uint64_t* state = nullptr;
-    bool lds = false;
-};
-
-int32_t groupPrepare(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupStage& G) {
-    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "group by: not a device-resident result");
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "group by: world > 1 needs mergeable partial states");
-    if (gp->nkeys < 1 || gp->nyields < 1 || !gp->key_cols || !gp->yields) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no key or yield columns");
-    if (gp->nkeys > kGroupMaxKeys) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 4 keys");
-    if (gp->nyields > kMaxDistinctCols) return fail(c, NGX_E_UNSUPPORTED, "group by: more than 64 yields");
-    const uint64_t n = G.n = r->nrows;
-    if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "group by: 2^32 rows or more");
-
-    std::vector<GroupCol>& cols = G.cols;
-    std::vector<int32_t> colOf(std::max<int32_t>(r->ncols, 1), -1);
-    std::vector<int32_t>& typeOf = G.typeOf;
-    auto useCol = [&](int32_t y, bool key, int32_t* idx) -> int32_t {
-        if (y < 0 || y >= r->ncols) return fail(c, NGX_E_BAD_ARGUMENT, "group by: no such result column");
-        const int32_t t = r->col_types[y];
-        if (t == 0 || (n && r->dev_cols[y].type)) return fail(c, NGX_E_UNSUPPORTED, "group by: UNKNOWN-typed column (per-row value types)");
-        if (t == NGX_T_FLOAT) return fail(c, NGX_E_UNSUPPORTED, "group by: FLOAT column");
-        if (key && t == NGX_T_DOUBLE) return fail(c, NGX_E_UNSUPPORTED, "group by: DOUBLE key column");
-        if (colOf[y] < 0) {
-            GroupCol gc{};
-            gc.kind = t == NGX_T_STRING ? kGroupString : t == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
-            gc.w = t == NGX_T_STRING || t == NGX_T_DOUBLE ? 8 : r->dev_col_w ? r->dev_col_w[y] : 8;
-            gc.konst = r->dev_col_const ? r->dev_col_const[y] : 0;
-            if (n) {
-                gc.x = gc.w ? r->dev_cols[y].x : nullptr;
-                gc.len = r->dev_cols[y].len;
-                if (gc.w && !gc.x) return fail(c, NGX_E_BAD_ARGUMENT, "group by: column without values");
-                if (gc.w != 0 && gc.w != 1 && gc.w != 2 && gc.w != 4 && gc.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "group by: column width");
-            }
-            colOf[y] = static_cast<int32_t>(cols.size());
-            cols.push_back(gc);
-            typeOf.push_back(t);
-        }
-        *idx = colOf[y];
-        return NGX_OK;
-    };
-    std::vector<int32_t>& keyIdx = G.keyIdx;
-    keyIdx.assign(gp->nkeys, -1);
-    for (int32_t k = 0; k < gp->nkeys; k++)
-        if (int32_t rc = useCol(gp->key_cols[k], true, &keyIdx[k])) return rc;
-
-    // per yield column: its state words and how its cell is finalised
-    std::vector<GroupSlot>& slots = G.slots;
-    std::vector<GroupEmit>& emit = G.emit;
-    std::vector<int32_t>& distinctCol = G.distinctCol;
-    emit.assign(gp->nyields, GroupEmit{});
-    G.isCount.assign(gp->nyields, 0);
-    auto slot = [&](int32_t op, int32_t src, int32_t col) {
-        GroupSlot s{};
-        s.op = op, s.src = src, s.col = col;
-        slots.push_back(s);
-        return static_cast<int32_t>(slots.size() - 1);
-    };
-    auto constant = [&](GroupEmit& e, int32_t kind, int64_t bits) { e.kind = kind, e.src = kEmitConst, e.konst = bits; };
-    for (int32_t y = 0; y < gp->nyields; y++) {
-        const ngx_agg_col& a = gp->yields[y];
-        GroupEmit& e = emit[y];
-        if (a.fn == NGX_AGG_STD) return fail(c, NGX_E_UNSUPPORTED, "group by: STD keeps every value of a group");
-        if (a.fn < NGX_AGG_GROUP || a.fn > NGX_AGG_BIT_XOR) return fail(c, NGX_E_BAD_ARGUMENT, "group by: unknown function");
-        int32_t ci = -1, t = 0;
-        if (a.col >= 0) {
-            if (int32_t rc = useCol(a.col, false, &ci)) return rc;
-            t = typeOf[ci];
-        } else {                                                  // a constant: a column of width 0
-            const int32_t k = a.konst.kind;
-            if (k != NGX_CELL_INT && k != NGX_CELL_DOUBLE && a.fn != NGX_AGG_COUNT && a.fn != NGX_AGG_COUNT_DISTINCT)
-                return fail(c, NGX_E_UNSUPPORTED, "group by: constant that is neither integer nor double");
-            t = k == NGX_CELL_INT ? NGX_T_INT : k == NGX_CELL_DOUBLE ? NGX_T_DOUBLE : NGX_T_STRING;
-            if (a.fn != NGX_AGG_GROUP && a.fn != NGX_AGG_COUNT && a.fn != NGX_AGG_COUNT_DISTINCT) {
-                GroupCol gc{};
-                gc.kind = t == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
-                gc.w = 0;
-                gc.konst = a.konst.v.i;
-                ci = static_cast<int32_t>(cols.size());
-                cols.push_back(gc);
-                typeOf.push_back(t);
-            }
-        }
-        switch (a.fn) {
-            case NGX_AGG_GROUP:
-                if (a.col < 0) { constant(e, a.konst.kind, a.konst.v.i); break; }
-                if (std::find(keyIdx.begin(), keyIdx.end(), ci) == keyIdx.end())
-                    return fail(c, NGX_E_UNSUPPORTED, "group by: a bare yield column that is not a key");
-                e.kind = t, e.src = kEmitKey, e.a = ci;
-                break;
-            case NGX_AGG_COUNT:
-                e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcOne, -1);
-                G.isCount[y] = 1;
-                break;
-            case NGX_AGG_COUNT_DISTINCT:
-                if (a.col < 0) { constant(e, NGX_CELL_INT, 1); break; }
-                e.kind = NGX_CELL_INT, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcFlag, static_cast<int32_t>(distinctCol.size()));
-                distinctCol.push_back(ci);
-                G.isCount[y] = 1;
-                break;
-            case NGX_AGG_SUM:
-                if (intLike(t)) e.kind = t, e.src = kEmitState, e.a = slot(kGroupAdd, kGroupSrcCol, ci);
-                else if (t == NGX_T_DOUBLE) e.kind = NGX_CELL_DOUBLE, e.src = kEmitState, e.a = slot(kGroupAddF64, kGroupSrcCol, ci);
-                else constant(e, NGX_CELL_INT, 0);                // Sum ignores values it cannot add
-                break;
-            case NGX_AGG_AVG:
-                if (t == NGX_T_VID || t == NGX_T_TIMESTAMP)
-                    return fail(c, NGX_E_UNSUPPORTED, "group by: AVG of a VID / TIMESTAMP column (the reference reads the sum as a double)");
-                e.kind = NGX_CELL_DOUBLE;
-                if (t == NGX_T_INT) e.src = kEmitAvgInt, e.a = slot(kGroupAdd, kGroupSrcCol, ci), slot(kGroupAdd, kGroupSrcOne, -1);
-                else if (t == NGX_T_DOUBLE) e.src = kEmitAvgF64, e.a = slot(kGroupAddF64, kGroupSrcCol, ci), slot(kGroupAdd, kGroupSrcOne, -1);
-                else constant(e, NGX_CELL_DOUBLE, 0);             // 0 / count
-                break;
-            case NGX_AGG_MAX:
-            case NGX_AGG_MIN: {
-                const int32_t op = a.fn == NGX_AGG_MAX ? kGroupMax : kGroupMin;
-                if (intLike(t)) e.kind = t, e.src = kEmitState, e.a = slot(op, kGroupSrcCol, ci);
-                else if (t == NGX_T_DOUBLE) e.kind = NGX_CELL_DOUBLE, e.src = kEmitOrdered, e.a = slot(op, kGroupSrcOrdered, ci);
-                else return fail(c, NGX_E_UNSUPPORTED, "group by: MAX / MIN of a BOOL or STRING column");
-                break;
-            }
-            default:                                              // BIT_*: integers only, anything else is ignored
-                if (t == NGX_T_INT)
-                    e.kind = NGX_CELL_INT, e.src = kEmitState,
-                    e.a = slot(a.fn == NGX_AGG_BIT_AND ? kGroupAnd : a.fn == NGX_AGG_BIT_OR ? kGroupOr : kGroupXor, kGroupSrcCol, ci);
-                else constant(e, NGX_CELL_INT, 0);
-                break;
-        }
-    }
-    return NGX_OK;
-}
-
-// assign + accumulate of a prepared stage with rows (G.n > 0)
-void groupAccumulate(ngx_ctx* c, const ngx_group_plan* gp, GroupStage& G) {
-    const uint64_t n = G.n;
-    std::vector<GroupCol>& cols = G.cols;
-    std::vector<GroupSlot>& slots = G.slots;
-    std::vector<GroupEmit>& emit = G.emit;
-    const std::vector<int32_t>& keyIdx = G.keyIdx;
-    const std::vector<int32_t>& distinctCol = G.distinctCol;
-
-    // ---- assign: leaders, group numbers
-    uint64_t cap = 1024;
-    while (cap < 2 * n) cap <<= 1;
-    GroupAssignArgs aa{};
-    aa.n = n;
-    aa.nk = gp->nkeys;
-    for (int32_t k = 0; k < gp->nkeys; k++) aa.k[k] = cols[keyIdx[k]];
-    aa.table = c->gbTable.get<uint64_t>(cap);
-    aa.mask = cap - 1;
-    aa.leader = c->gbLeader.get<uint32_t>(n);
-    aa.flag = c->gbFlag.get<uint64_t>(n + 1);
-    uint64_t* pre = c->gbPre.get<uint64_t>(n + 1);
-    uint64_t* tiles = c->gbTiles.get<uint64_t>((n + kTile - 1) / kTile + 1);
-    uint64_t* dflags = c->gbDistinct.get<uint64_t>(std::max<uint64_t>(distinctCol.size(), 1) * n);
-    c->timed("group_assign", n * 8 * static_cast<uint64_t>(gp->nkeys), [&] {
-        HIP_OK(hipMemsetAsync(aa.table, 0, cap * 8, c->stream));
-        if (launchGroupAssign(aa, c->stream)) throw Error{NGX_E_DEVICE, "group assign"};
-        if (launchScanU64(aa.flag, n, pre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "group scan"};
-        for (size_t d = 0; d < distinctCol.size(); d++) {         // (keys, value) leaders per COUNT_DISTINCT
-            GroupAssignArgs da = aa;
-            da.k[da.nk++] = cols[distinctCol[d]];
-            da.leader = nullptr;
-            da.flag = dflags + d * n;
-            HIP_OK(hipMemsetAsync(da.table, 0, cap * 8, c->stream));
-            if (launchGroupAssign(da, c->stream)) throw Error{NGX_E_DEVICE, "group distinct"};
-        }
-    });
-    const uint64_t ngroups = readScalar(c, pre + n);
-    if (ngroups == 0 || ngroups > n) throw Error{NGX_E_DEVICE, "group by: group count out of range"};
-
-    // ---- accumulate
-    const size_t descBytes = cols.size() * sizeof(GroupCol) + slots.size() * sizeof(GroupSlot) + emit.size() * sizeof(GroupEmit);
-    char* desc = c->gbDesc.get<char>(descBytes);
-    GroupCol* colsDev = reinterpret_cast<GroupCol*>(desc);
-    GroupSlot* slotsDev = reinterpret_cast<GroupSlot*>(colsDev + cols.size());
-    GroupEmit* emitDev = reinterpret_cast<GroupEmit*>(slotsDev + slots.size());
-    for (GroupSlot& s : slots)
-        if (s.src == kGroupSrcFlag) s.flag = dflags + static_cast<uint64_t>(s.col) * n;
-    HIP_OK(hipMemcpyAsync(colsDev, cols.data(), cols.size() * sizeof(GroupCol), hipMemcpyHostToDevice, c->stream));
-    if (!slots.empty())
-        HIP_OK(hipMemcpyAsync(slotsDev, slots.data(), slots.size() * sizeof(GroupSlot), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(emitDev, emit.data(), emit.size() * sizeof(GroupEmit), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vectors are pageable: copied before they go
-    GroupAccumArgs ga{};
-    ga.n = n;
-    ga.ngroups = ngroups;
-    ga.nslots = static_cast<int32_t>(slots.size());
-    ga.slots = slotsDev;
-    ga.cols = colsDev;
-    ga.leader = aa.leader;
-    ga.pre = pre;
-    ga.state = c->gbState.get<uint64_t>(std::max<uint64_t>(ngroups * slots.size(), 1));
-    const uint64_t stateBytes = ngroups * slots.size() * 8;
-    // LDS when the workgroup's copy is small next to the rows it folds (by default up to 32 KiB of state)
-    const bool lds = !slots.empty() && stateBytes <= kGroupLdsBytes &&
-                     (c->groupLdsMax < 0 ? stateBytes <= 32 * 1024 : ngroups <= static_cast<uint64_t>(c->groupLdsMax));
-    c->timed(lds ? "group_accum_lds" : "group_accum", n * 8 * (slots.size() + 1), [&] {
-        if (launchGroupAccum(ga, lds, c->groupGridMax, c->stream)) throw Error{NGX_E_DEVICE, "group accumulate"};
-    });
-    G.ngroups = ngroups;
-    G.colsDev = colsDev, G.slotsDev = slotsDev, G.emitDev = emitDev;
-    G.leader = aa.leader, G.flag = aa.flag, G.pre = pre, G.tiles = tiles, G.state = ga.state;
-    G.lds = lds;
-}
-
-void groupEvents(ngx_ctx* c) {
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-}
-
-int32_t groupBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, GroupResultHolder& R) {
-    GroupStage G;
-    if (int32_t rc = groupPrepare(c, r, gp, G)) return rc;
-    const uint64_t n = G.n;
-    const std::vector<GroupCol>& cols = G.cols;
-    const std::vector<GroupEmit>& emit = G.emit;
-    R.r.ncols = gp->nyields;
-    R.colTypes.assign(gp->nyields, 0);
-    R.r.col_types = R.colTypes.data();
-    if (n == 0) {
-        c->groupByDevice++;
-        return NGX_OK;
-    }
-    for (int32_t y = 0; y < gp->nyields; y++) R.colTypes[y] = emit[y].kind;
-
-    groupEvents(c);
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
-    groupAccumulate(c, gp, G);
-    const uint64_t ngroups = G.ngroups;
-    uint64_t* tiles = G.tiles;
-    const bool lds = G.lds;
-
-    // ---- emit
-    GroupEmitArgs ea{};
-    ea.n = n;
-    ea.ngroups = ngroups;
-    ea.ny = gp->nyields;
-    ea.emit = G.emitDev;
-    ea.cols = G.colsDev;
-    ea.flag = G.flag;
-    ea.pre = G.pre;
-    ea.state = G.state;
-    ea.cells = c->gbCells.get<GroupCell>(ngroups * gp->nyields);
-    bool anyString = false;
-    for (const GroupEmit& e : emit) anyString |= e.src == kEmitKey && cols[e.a].kind == kGroupString;
-    uint64_t strBytes = 0;
-    if (anyString) {
-        uint64_t* slen = c->gbSlen.get<uint64_t>(n + 1);
-        uint64_t* spre = c->gbSpre.get<uint64_t>(n + 1);
-        if (launchGroupStrLen(ea, slen, c->stream)) throw Error{NGX_E_DEVICE, "group string lengths"};
-        if (launchScanU64(slen, n, spre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "group string scan"};
-        strBytes = readScalar(c, spre + n);
-        ea.strPre = spre;
-        ea.strOut = c->gbStr.get<char>(std::max<uint64_t>(strBytes, 1));
-    }
-    c->timed("group_emit", ngroups * gp->nyields * sizeof(GroupCell), [&] {
-        if (launchGroupEmit(ea, c->stream)) throw Error{NGX_E_DEVICE, "group emit"};
-    });
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    R.cells.resize(ngroups * gp->nyields);
-    HIP_OK(hipMemcpyAsync(R.cells.data(), ea.cells, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
-    R.strings.resize(strBytes);
-    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], ea.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.r.device_ms = ms;
-    R.r.ngroups = ngroups;
-    R.r.cells = R.cells.data();
-    R.r.strings = R.strings.data();
-    R.r.strings_len = strBytes;
-    c->groupByDevice++;
-    if (lds) c->groupByLds++;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_go_group_by(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* plan, ngx_group_result** out) {
-    if (!c || !r || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<GroupResultHolder>();
-    int32_t rc;
-    try {
-        rc = groupBy(c, r, plan, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_group_result_free(ngx_group_result* r) {
-    if (r) delete reinterpret_cast<GroupResultHolder*>(r);
-}
-
-// ============================================================================ ORDER BY / LIMIT
-namespace {
-
-struct OrderResultHolder {
-    ngx_order_result r{};
-    std::vector<int32_t> colTypes;
-    std::vector<ngx_cell> cells;
-    std::string strings;
-};
-
-// the word the device orders a double by (orderby.hip kOrdDouble): the winners' host sort uses the same
-uint64_t orderDoubleKey(int64_t bits) {
-    uint64_t b = static_cast<uint64_t>(bits);
-    double d;
-    std::memcpy(&d, &b, sizeof d);
-    if (d == 0.0) b = 0;
-    return b ^ (static_cast<uint64_t>(static_cast<int64_t>(b) >> 63) | 0x8000000000000000ULL);
-}
-
-// the plan's own limits, before any column is looked at
-int32_t orderPlanCheck(ngx_ctx* c, const ngx_order_plan* op) {
-    if (op->nfactors < 0 || (op->nfactors && !op->factors) || op->offset < 0) return fail(c, NGX_E_BAD_ARGUMENT, "order by: factors or offset");
-    if (op->count < 0) return fail(c, NGX_E_UNSUPPORTED, "order by: no LIMIT (every row crosses anyway)");
-    if (op->nfactors > kOrderMaxFactors) return fail(c, NGX_E_UNSUPPORTED, "order by: more than 8 factors");
-    if (op->offset > c->orderKMax || op->count > c->orderKMax - op->offset)
-        return fail(c, NGX_E_UNSUPPORTED, "order by: offset + count above order_k_max");
-    return NGX_OK;
-}
-
-int32_t orderRows(ngx_ctx* c, uint64_t n, int32_t ncols, const int32_t* types, const std::vector<OrderEmitCol>& ecols, bool anyString,
-                  const ngx_order_plan* op, bool started, OrderResultHolder& R);
-
-int32_t orderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* op, OrderResultHolder& R) {
-    if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "order by: not a device-resident result");
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "order by: world > 1 needs the shards' winners merged");
-    if (int32_t rc = orderPlanCheck(c, op)) return rc;
-    const uint64_t n = r->nrows;
-    if (n >= (1ULL << 32)) return fail(c, NGX_E_UNSUPPORTED, "order by: 2^32 rows or more");
-    const int32_t ncols = r->ncols;
-    for (int32_t f = 0; f < op->nfactors; f++) {
-        const int32_t y = op->factors[f].col;
-        if (y < 0 || y >= ncols) return fail(c, NGX_E_BAD_ARGUMENT, "order by: no such result column");
-        if (r->col_types[y] == 0 || (n && r->dev_cols[y].type))
-            return fail(c, NGX_E_UNSUPPORTED, "order by: UNKNOWN-typed factor column (per-row value types)");
-    }
-    R.r.input_rows = n;
-    R.r.ncols = ncols;
-    R.colTypes.assign(r->col_types, r->col_types + ncols);
-    R.r.col_types = R.colTypes.data();
-    if (op->count == 0 || static_cast<uint64_t>(op->offset) >= n || ncols == 0) {   // the column names and no rows: nothing to launch
-        c->orderByDevice++;
-        return NGX_OK;
-    }
-
-    // every column as the emit kernel reads it; the factors' among them feed the levels
-    std::vector<OrderEmitCol> ecols(ncols);
-    bool anyString = false;
-    for (int32_t y = 0; y < ncols; y++) {
-        const int32_t t = r->col_types[y];
-        OrderEmitCol& e = ecols[y];
-        e.type = r->dev_cols[y].type;
-        if (t == 0 && !e.type) return fail(c, NGX_E_UNSUPPORTED, "order by: a column of UNKNOWN type without per-row types");
-        e.cell = t;                                               // NGX_CELL_* numbers its kinds as NGX_T_*
-        e.c.kind = t == NGX_T_STRING ? kGroupString : t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? kGroupDouble : kGroupInt;
-        e.c.w = e.type || t == NGX_T_STRING || t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? 8 : r->dev_col_w ? r->dev_col_w[y] : 8;
-        e.c.konst = r->dev_col_const ? r->dev_col_const[y] : 0;
-        e.c.x = e.c.w ? r->dev_cols[y].x : nullptr;
-        e.c.len = r->dev_cols[y].len;
-        if (e.c.w && !e.c.x) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column without values");
-        if (e.c.w != 0 && e.c.w != 1 && e.c.w != 2 && e.c.w != 4 && e.c.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "order by: column width");
-        anyString |= t == NGX_T_STRING || e.type != nullptr;
-    }
-    if (int32_t rc = orderRows(c, n, ncols, r->col_types, ecols, anyString, op, false, R)) return rc;
-    c->orderByDevice++;
-    return NGX_OK;
-}
-
-// Levels -> select -> emit -> host sort of the winners, over n rows of ncols columns as the kernels read them
-// (a GO result's columns for ngx_go_order_by, the group columns for ngx_go_group_order_by; types: NGX_T_* per
-// column). The window has rows (count > 0, offset < n, ncols > 0). started: the caller recorded gbEv[0] already
-// and device_ms counts from there.
-int32_t orderRows(ngx_ctx* c, uint64_t n, int32_t ncols, const int32_t* types, const std::vector<OrderEmitCol>& ecols, bool anyString,
-                  const ngx_order_plan* op, bool started, OrderResultHolder& R) {
-    const uint64_t offset = static_cast<uint64_t>(op->offset), K = offset + static_cast<uint64_t>(op->count);
-    std::vector<GroupCol> cols(ncols);
-    for (int32_t y = 0; y < ncols; y++) cols[y] = ecols[y].c;
-
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    if (!started) HIP_OK(hipEventRecord(ev0, c->stream));
-
-    // ---- the levels: per factor its words, then the row index
-    std::vector<OrderLevel> levels;
-    auto bitsFor = [](uint64_t maxValue) {
-        int32_t bits = 8;
-        while (bits < 64 && (maxValue >> bits)) bits += 8;
-        return bits;
-    };
-    for (int32_t f = 0; f < op->nfactors; f++) {
-        const int32_t y = op->factors[f].col, t = types[y];
-        const int32_t desc = op->factors[f].desc ? 1 : 0;
-        if (t == NGX_T_STRING) {
-            uint32_t* mx = c->obMax.get<uint32_t>(1);
-            if (launchOrderMaxLen(cols[y].len, n, mx, c->stream)) throw Error{NGX_E_DEVICE, "order max length"};
-            const uint32_t maxLen = readScalar(c, mx);
-            if (maxLen > kOrderMaxStr) return fail(c, NGX_E_UNSUPPORTED, "order by: a factor string longer than 256 bytes");
-            for (uint32_t w = 0; w < (maxLen + 7) / 8; w++) levels.push_back(OrderLevel{y, kOrdStrWord, static_cast<int32_t>(w), desc, 64, 0});
-            if (maxLen) levels.push_back(OrderLevel{y, kOrdStrLen, 0, desc, bitsFor(maxLen), 0});
-        } else if ((t == NGX_T_DOUBLE || t == NGX_T_FLOAT) && cols[y].w) {
-            levels.push_back(OrderLevel{y, kOrdDouble, 0, desc, 64, 0});
-        } else if (cols[y].w) {                                   // width 0: a constant ties every row
-            levels.push_back(OrderLevel{y, kOrdInt, 0, desc, cols[y].w * 8, 0});
-        }
-    }
-    const bool select = !levels.empty() && K < n;                 // else the winners are a range of rows as stored
-    levels.push_back(OrderLevel{0, kOrdRow, 0, 0, bitsFor(n - 1), 0});
-
-    // ---- descriptors
-    const size_t descBytes = cols.size() * sizeof(GroupCol) + ecols.size() * sizeof(OrderEmitCol) + levels.size() * sizeof(OrderLevel);
-    char* desc = c->obDesc.get<char>(descBytes);
-    OrderEmitCol* ecolsDev = reinterpret_cast<OrderEmitCol*>(desc);
-    GroupCol* colsDev = reinterpret_cast<GroupCol*>(ecolsDev + ecols.size());
-    OrderLevel* levelsDev = reinterpret_cast<OrderLevel*>(colsDev + cols.size());
-    HIP_OK(hipMemcpyAsync(ecolsDev, ecols.data(), ecols.size() * sizeof(OrderEmitCol), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(colsDev, cols.data(), cols.size() * sizeof(GroupCol), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(levelsDev, levels.data(), levels.size() * sizeof(OrderLevel), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vectors are pageable: copied before they go
-
-    // ---- select: the rows of the K first places, in no order
-    OrderEmitArgs ea{};
-    ea.n = n;
-    ea.ncols = ncols;
-    ea.cols = ecolsDev;
-    if (select) {
-        OrderArgs oa{};
-        oa.n = n;
-        oa.cols = colsDev;
-        oa.levels = levelsDev;
-        oa.nlevels = static_cast<int32_t>(levels.size());
-        oa.mark = c->obMark.get<uint8_t>(n);
-        oa.listCap = n / kOrderCompactDiv + 1;
-        oa.list[0] = c->obList[0].get<uint32_t>(oa.listCap);
-        oa.list[1] = c->obList[1].get<uint32_t>(oa.listCap);
-        oa.hist = c->obHist.get<uint64_t>(256);
-        oa.S = c->obState.get<OrderState>(1);
-        oa.win = c->obWin.get<uint32_t>(K);
-        oa.winCap = K;
-        oa.gridMax = c->orderGridMax;
-        OrderState st{};
-        st.rank = K - 1;
-        st.nTied = n;
-        HIP_OK(hipMemsetAsync(oa.mark, kOrdTied, n, c->stream));
-        HIP_OK(hipMemsetAsync(oa.hist, 0, 256 * sizeof(uint64_t), c->stream));
-        HIP_OK(hipMemcpyAsync(oa.S, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));                  // st is on the stack
-        uint64_t bytes = 0;
-        for (const OrderLevel& L : levels) bytes += n * static_cast<uint64_t>(L.bits / 8 + 1);   // upper bound: every step over all rows
-        c->timed("order_select", bytes, [&] {
-            for (size_t l = 0; l < levels.size(); l++) {
-                for (int shift = levels[l].bits - 8; shift >= 0; shift -= 8)
-                    if (launchOrderStep(oa, static_cast<int>(l), shift, l + 1 == levels.size() && shift == 0, c->stream))
-                        throw Error{NGX_E_DEVICE, "order step"};
-                HIP_OK(hipMemcpyAsync(&st, oa.S, sizeof st, hipMemcpyDeviceToHost, c->stream));   // once per level, not per digit
-                HIP_OK(hipStreamSynchronize(c->stream));
-                if (st.err) throw Error{NGX_E_DEVICE, "order by: inconsistent counts"};
-                if (st.done) break;
-            }
-            if (launchOrderGather(oa, c->stream)) throw Error{NGX_E_DEVICE, "order gather"};
-        });
-        HIP_OK(hipMemcpyAsync(&st, oa.S, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        c->orderCompactions += st.compactions;
-        c->orderListCompactions += st.listCompactions;
-        c->orderLoopFlushes += st.loopFlushes;
-        if (st.err || !st.done || st.nWin != K) throw Error{NGX_E_DEVICE, "order by: winner count out of range"};
-        ea.rows = oa.win;
-        ea.m = K;
-    } else if (levels.size() == 1) {                              // LIMIT alone, or only constant factors: rows as stored
-        ea.base = offset;
-        ea.m = std::min(K, n) - offset;
-    } else {                                                      // K >= n: every row, ordered below
-        ea.m = n;
-    }
-    const uint64_t m = ea.m;
-
-    // ---- emit
-    ea.cells = c->obCells.get<GroupCell>(m * ncols);
-    uint64_t strBytes = 0;
-    if (anyString) {
-        uint64_t* slen = c->obSlen.get<uint64_t>(m + 1);
-        uint64_t* spre = c->obSpre.get<uint64_t>(m + 1);
-        uint64_t* tiles = c->obTiles.get<uint64_t>((m + kTile - 1) / kTile + 1);
-        if (launchOrderStrLen(ea, slen, c->stream)) throw Error{NGX_E_DEVICE, "order string lengths"};
-        if (launchScanU64(slen, m, spre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "order string scan"};
-        strBytes = readScalar(c, spre + m);
-        ea.strPre = spre;
-        ea.strOut = c->obStr.get<char>(std::max<uint64_t>(strBytes, 1));
-    }
-    c->timed("order_emit", m * ncols * sizeof(GroupCell) + strBytes, [&] {
-        if (launchOrderEmit(ea, c->stream)) throw Error{NGX_E_DEVICE, "order emit"};
-    });
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    std::vector<ngx_cell> cells(m * ncols);
-    std::vector<uint32_t> rows(m);
-    HIP_OK(hipMemcpyAsync(cells.data(), ea.cells, cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
-    if (ea.rows) HIP_OK(hipMemcpyAsync(rows.data(), ea.rows, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    R.strings.resize(strBytes);
-    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], ea.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.r.device_ms = ms;
-
-    // ---- the winners in order (factors, then the row index), less the first `offset`
-    const auto t0 = std::chrono::steady_clock::now();
-    if (levels.size() == 1) {
-        R.cells = std::move(cells);
-    } else {
-        if (!ea.rows)
-            for (uint64_t i = 0; i < m; i++) rows[i] = static_cast<uint32_t>(i);
-        std::vector<uint32_t> perm(m);
-        for (uint64_t i = 0; i < m; i++) perm[i] = static_cast<uint32_t>(i);
-        const char* sbase = R.strings.data();
-        auto less = [&](uint32_t a, uint32_t b) {
-            for (int32_t f = 0; f < op->nfactors; f++) {
-                const int32_t y = op->factors[f].col, t = types[y];
-                const ngx_cell* x = &cells[static_cast<uint64_t>(a) * ncols + y];
-                const ngx_cell* z = &cells[static_cast<uint64_t>(b) * ncols + y];
-                if (op->factors[f].desc) std::swap(x, z);
-                if (t == NGX_T_STRING) {
-                    const size_t common = static_cast<size_t>(std::min(x->str_len, z->str_len));
-                    const int cmp = common ? std::memcmp(sbase + x->v.str_off, sbase + z->v.str_off, common) : 0;
-                    if (cmp) return cmp < 0;
-                    if (x->str_len != z->str_len) return x->str_len < z->str_len;
-                } else if (t == NGX_T_DOUBLE || t == NGX_T_FLOAT) {
-                    const uint64_t kx = orderDoubleKey(x->v.i), kz = orderDoubleKey(z->v.i);
-                    if (kx != kz) return kx < kz;
-                } else if (x->v.i != z->v.i) {
-                    return x->v.i < z->v.i;
-                }
-            }
-            return rows[a] < rows[b];
-        };
-        std::sort(perm.begin(), perm.end(), less);
-        const uint64_t keep = m > offset ? m - offset : 0;
-        R.cells.resize(keep * ncols);
-        for (uint64_t i = 0; i < keep; i++)
-            std::memcpy(&R.cells[i * ncols], &cells[static_cast<uint64_t>(perm[offset + i]) * ncols], ncols * sizeof(ngx_cell));
-    }
-    R.r.host_sort_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    R.r.nrows = ncols ? R.cells.size() / ncols : 0;
-    R.r.cells = R.cells.data();
-    R.r.strings = R.strings.data();
-    R.r.strings_len = strBytes;
-    return NGX_OK;
-}
-
-// GO | GROUP BY | [ORDER BY |] LIMIT: the grouping's state becomes columns (k_group_columns) and the select
-// reads those; only the window's group rows cross.
-int32_t groupOrderBy(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* gp, const ngx_order_plan* op, OrderResultHolder& R) {
-    GroupStage G;
-    if (int32_t rc = groupPrepare(c, r, gp, G)) return rc;
-    if (int32_t rc = orderPlanCheck(c, op)) return rc;
-    const int32_t ny = gp->nyields;
-    for (int32_t f = 0; f < op->nfactors; f++)
-        if (op->factors[f].col < 0 || op->factors[f].col >= ny) return fail(c, NGX_E_BAD_ARGUMENT, "order by: no such result column");
-    const uint64_t n = G.n;
-    R.r.ncols = ny;
-    R.colTypes.assign(ny, 0);
-    R.r.col_types = R.colTypes.data();
-    if (n == 0) {                                                 // no groups: nothing to launch
-        c->groupOrderDevice++;
-        return NGX_OK;
-    }
-    for (int32_t y = 0; y < ny; y++) R.colTypes[y] = G.emit[y].kind;
-
-    groupEvents(c);
-    HIP_OK(hipEventRecord(c->gbEv[0], c->stream));
-    groupAccumulate(c, gp, G);
-    const uint64_t ngroups = G.ngroups;
-    R.r.input_rows = ngroups;
-
-    // ---- the group rows as columns: a COUNT / COUNT_DISTINCT lies in [0, n] and takes the narrowest signed
-    // width that holds n (the select pays one step per byte of an integer factor); the rest 8 bytes
-    const int32_t countW = n <= 0x7F ? 1 : n <= 0x7FFF ? 2 : n <= 0x7FFFFFFF ? 4 : 8;
-    std::vector<GroupColumnOut> outs(ny);
-    std::vector<OrderEmitCol> ecols(ny);
-    uint64_t colBytes = 0, lenCols = 0;
-    bool anyString = false;
-    for (int32_t y = 0; y < ny; y++) {
-        const GroupEmit& e = G.emit[y];
-        OrderEmitCol& oc = ecols[y];
-        oc.cell = e.kind;                                         // NGX_CELL_* numbers its kinds as NGX_T_*
-        oc.c.kind = e.kind == NGX_T_STRING ? kGroupString : e.kind == NGX_T_DOUBLE ? kGroupDouble : kGroupInt;
-        oc.c.konst = e.konst;
-        oc.c.w = e.src == kEmitConst ? 0 : G.isCount[y] ? countW : 8;
-        outs[y].w = oc.c.w;
-        colBytes += (ngroups * static_cast<uint64_t>(oc.c.w) + 7) / 8 * 8;
-        if (oc.c.kind == kGroupString) lenCols++, anyString = true;
-    }
-    char* colMem = c->goCols.get<char>(std::max<uint64_t>(colBytes, 1));
-    uint32_t* lenMem = c->goLen.get<uint32_t>(std::max<uint64_t>(lenCols * ngroups, 1));
-    uint64_t at = 0, lenAt = 0;
-    for (int32_t y = 0; y < ny; y++) {
-        OrderEmitCol& oc = ecols[y];
-        if (!oc.c.w) continue;
-        outs[y].x = colMem + at;
-        oc.c.x = outs[y].x;
-        at += (ngroups * static_cast<uint64_t>(oc.c.w) + 7) / 8 * 8;
-        if (oc.c.kind == kGroupString) {
-            outs[y].len = lenMem + lenAt;
-            oc.c.len = outs[y].len;
-            lenAt += ngroups;
-        }
-    }
-    GroupColumnOut* outsDev = c->goDesc.get<GroupColumnOut>(ny);
-    HIP_OK(hipMemcpyAsync(outsDev, outs.data(), outs.size() * sizeof(GroupColumnOut), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vector is pageable: copied before it goes
-    GroupColumnsArgs ca{};
-    ca.n = n;
-    ca.ngroups = ngroups;
-    ca.ny = ny;
-    ca.emit = G.emitDev;
-    ca.cols = G.colsDev;
-    ca.flag = G.flag;
-    ca.pre = G.pre;
-    ca.state = G.state;
-    ca.out = outsDev;
-    c->timed("group_columns", n * 8 + colBytes + lenCols * ngroups * 4, [&] {
-        if (launchGroupColumns(ca, c->stream)) throw Error{NGX_E_DEVICE, "group columns"};
-    });
-
-    int32_t rc = NGX_OK;
-    if (op->count != 0 && static_cast<uint64_t>(op->offset) < ngroups)
-        rc = orderRows(c, ngroups, ny, R.colTypes.data(), ecols, anyString, op, true, R);
-    else
-        HIP_OK(hipStreamSynchronize(c->stream));
-    c->collectTimings();
-    if (rc) return rc;
-    c->groupOrderDevice++;
-    if (G.lds) c->groupByLds++;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_go_order_by(ngx_ctx* c, const ngx_go_result* r, const ngx_order_plan* plan, ngx_order_result** out) {
-    if (!c || !r || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<OrderResultHolder>();
-    int32_t rc;
-    try {
-        rc = orderBy(c, r, plan, *R);
-    } catch (const Error& e) {
-        (void)hipStreamSynchronize(c->stream);                    // no kernel left reading the descriptors
-        rc = fail(c, e.code, e.msg);
-    }
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_order_result_free(ngx_order_result* r) {
-    if (r) delete reinterpret_cast<OrderResultHolder*>(r);
-}
-
-extern "C" int32_t ngx_go_group_order_by(ngx_ctx* c, const ngx_go_result* r, const ngx_group_plan* group, const ngx_order_plan* order,
-                                         ngx_order_result** out) {
-    if (!c || !r || !group || !order || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<OrderResultHolder>();
-    int32_t rc;
-    try {
-        rc = groupOrderBy(c, r, group, order, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-// ============================================================================ UNION DISTINCT / INTERSECT / MINUS
-namespace {
-
-struct SetResultHolder {
-    ngx_set_result r{};
-    std::vector<int32_t> colTypes;
-    std::vector<ngx_cell> cells;
-    std::string strings;
-};
-
-// one side's columns as the kernels read them (as orderBy lays a GO result's columns out)
-int32_t setColumns(ngx_ctx* c, const ngx_go_result* r, std::vector<OrderEmitCol>& ecols) {
-    ecols.assign(r->ncols, OrderEmitCol{});
-    for (int32_t y = 0; y < r->ncols; y++) {
-        const int32_t t = r->col_types[y];
-        OrderEmitCol& e = ecols[y];
-        e.cell = t;                                               // NGX_CELL_* numbers its kinds as NGX_T_*
-        e.c.kind = t == NGX_T_STRING ? kGroupString : t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? kGroupDouble : kGroupInt;
-        e.c.w = t == NGX_T_STRING || t == NGX_T_DOUBLE || t == NGX_T_FLOAT ? 8 : r->dev_col_w ? r->dev_col_w[y] : 8;
-        e.c.konst = r->dev_col_const ? r->dev_col_const[y] : 0;
-        if (!r->nrows) continue;
-        e.c.x = e.c.w ? r->dev_cols[y].x : nullptr;
-        e.c.len = r->dev_cols[y].len;
-        if (e.c.w && !e.c.x) return fail(c, NGX_E_BAD_ARGUMENT, "set op: column without values");
-        if (e.c.w != 0 && e.c.w != 1 && e.c.w != 2 && e.c.w != 4 && e.c.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "set op: column width");
-        if (t == NGX_T_STRING && !e.c.len) return fail(c, NGX_E_BAD_ARGUMENT, "set op: string column without lengths");
-    }
-    return NGX_OK;
-}
-
-int32_t setOp(ngx_ctx* c, const ngx_go_result* L, const ngx_go_result* Rt, const ngx_set_plan* sp, SetResultHolder& R) {
-    const ngx_go_result* side[2] = {L, Rt};
-    for (const ngx_go_result* r : side)
-        if (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols)) return fail(c, NGX_E_BAD_ARGUMENT, "set op: not a device-resident result");
-    if (sp->op == NGX_SET_UNION_ALL) return fail(c, NGX_E_UNSUPPORTED, "set op: UNION ALL needs no kernel (the caller concatenates)");
-    if (sp->op != NGX_SET_UNION_DISTINCT && sp->op != NGX_SET_INTERSECT && sp->op != NGX_SET_MINUS)
-        return fail(c, NGX_E_BAD_ARGUMENT, "set op: unknown operator");
-    if (L->ncols != Rt->ncols) return fail(c, NGX_E_BAD_ARGUMENT, "Field count not match.");      // SetExecutor.cpp:166-171
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "set op: world > 1 needs the shards' tables merged");
-    const int32_t ncols = L->ncols;
-    if (ncols > kSetMaxCols) return fail(c, NGX_E_UNSUPPORTED, "set op: more than 16 columns");
-    const uint64_t n[2] = {L->nrows, Rt->nrows};
-    R.r.left_rows = n[0];
-    R.r.right_rows = n[1];
-    R.r.ncols = ncols;
-    R.colTypes.assign(L->col_types, L->col_types + ncols);
-    R.r.col_types = R.colTypes.data();
-    if (ncols == 0 || (n[0] == 0 && n[1] == 0)) {                 // onEmptyInputs: the column names and no rows
-        c->setOpDevice++;
-        return NGX_OK;
-    }
-    // one side empty (SetExecutor.cpp:202-213, 308-312, 358-368): the other side as it is, or nothing; no table
-    int pass = -1;                                                // the side handed through whole
-    if (n[0] == 0 || n[1] == 0) {
-        if (sp->op == NGX_SET_UNION_DISTINCT) pass = n[0] ? 0 : 1;
-        else if (sp->op == NGX_SET_MINUS && n[0]) pass = 0;
-        else {
-            c->setOpDevice++;
-            return NGX_OK;
-        }
-    }
-    for (int s = 0; s < 2; s++)
-        for (int32_t y = 0; y < ncols; y++)
-            if (side[s]->col_types[y] == 0 || (n[s] && side[s]->dev_cols[y].type))
-                return fail(c, NGX_E_UNSUPPORTED, "set op: UNKNOWN-typed column (per-row value types)");
-    if (pass < 0)
-        for (int32_t y = 0; y < ncols; y++)
-            if (L->col_types[y] != Rt->col_types[y]) return fail(c, NGX_E_UNSUPPORTED, "set op: column types differ (casting stays on the host)");
-    if (n[0] >= (1ULL << 31) || n[1] >= (1ULL << 31)) return fail(c, NGX_E_UNSUPPORTED, "set op: 2^31 rows or more on a side");
-    if (pass >= 0 && n[pass] > static_cast<uint64_t>(c->setRowsMax)) return fail(c, NGX_E_UNSUPPORTED, "set op: output rows above set_rows_max");
-    if (pass == 1) R.colTypes.assign(Rt->col_types, Rt->col_types + ncols);
-
-    std::vector<OrderEmitCol> ecols[2];
-    bool anyString = false;
-    for (int s = 0; s < 2; s++) {
-        if (int32_t rc = setColumns(c, side[s], ecols[s])) return rc;
-        for (const OrderEmitCol& e : ecols[s]) anyString |= e.c.kind == kGroupString;
-    }
-
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
-
-    // ---- descriptors: per side its emit columns, then its key columns
-    const size_t perSide = ncols * (sizeof(OrderEmitCol) + sizeof(GroupCol));
-    char* desc = c->sbDesc.get<char>(2 * perSide);
-    OrderEmitCol* ecolsDev[2];
-    GroupCol* colsDev[2];
-    std::vector<GroupCol> cols[2];
-    for (int s = 0; s < 2; s++) {
-        ecolsDev[s] = reinterpret_cast<OrderEmitCol*>(desc + s * perSide);
-        colsDev[s] = reinterpret_cast<GroupCol*>(ecolsDev[s] + ncols);
-        cols[s].resize(ncols);
-        for (int32_t y = 0; y < ncols; y++) cols[s][y] = ecols[s][y].c;
-        HIP_OK(hipMemcpyAsync(ecolsDev[s], ecols[s].data(), ncols * sizeof(OrderEmitCol), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(colsDev[s], cols[s].data(), ncols * sizeof(GroupCol), hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_OK(hipStreamSynchronize(c->stream));                      // the host vectors are pageable: copied before they go
-
-    // ---- build and probe: the kept rows of either side, in no order
-    std::vector<uint32_t> kept[2];
-    uint32_t* keepDev[2] = {nullptr, nullptr};
-    if (pass < 0) {
-        // a string longer than kOrderMaxStr in a key column: one lane would hash and compare it byte by byte
-        if (anyString) {
-            uint32_t* mx = c->obMax.get<uint32_t>(1);
-            for (int s = 0; s < 2; s++)
-                for (int32_t y = 0; y < ncols; y++) {
-                    if (cols[s][y].kind != kGroupString) continue;
-                    if (launchOrderMaxLen(cols[s][y].len, n[s], mx, c->stream)) throw Error{NGX_E_DEVICE, "set max length"};
-                    if (readScalar(c, mx) > kOrderMaxStr) return fail(c, NGX_E_UNSUPPORTED, "set op: a string longer than 256 bytes");
-                }
-        }
-        const bool uni = sp->op == NGX_SET_UNION_DISTINCT;
-        const uint64_t nBuild = uni ? n[0] + n[1] : n[1];
-        uint64_t slots = 64;
-        while (slots < 2 * nBuild) slots <<= 1;
-        SetArgs a{};
-        a.n[0] = n[0];
-        a.n[1] = n[1];
-        a.cols[0] = colsDev[0];
-        a.cols[1] = colsDev[1];
-        a.nc = ncols;
-        a.op = uni ? kSetUnionDistinct : sp->op == NGX_SET_INTERSECT ? kSetIntersect : kSetMinus;
-        a.table = c->sbTable.get<uint64_t>(slots);
-        a.mask = slots - 1;
-        HIP_OK(hipMemsetAsync(a.table, 0, slots * sizeof(uint64_t), c->stream));
-        if (a.op == kSetIntersect) {
-            a.count = c->sbCount.get<uint32_t>(slots);
-            a.taken = c->sbTaken.get<uint32_t>(slots);
-            HIP_OK(hipMemsetAsync(a.count, 0, slots * sizeof(uint32_t), c->stream));
-            HIP_OK(hipMemsetAsync(a.taken, 0, slots * sizeof(uint32_t), c->stream));
-        }
-        a.keep[0] = keepDev[0] = c->sbKeep[0].get<uint32_t>(std::max<uint64_t>(n[0], 1));
-        a.keep[1] = keepDev[1] = c->sbKeep[1].get<uint32_t>(std::max<uint64_t>(n[1], 1));
-        a.S = c->sbState.get<SetState>(1);
-        a.gridMax = c->setGridMax;
-        HIP_OK(hipMemsetAsync(a.S, 0, sizeof(SetState), c->stream));
-        uint64_t rowBytes[2] = {0, 0};                            // value bytes a pass over a side's rows reads
-        for (int s = 0; s < 2; s++)
-            for (const GroupCol& g : cols[s]) rowBytes[s] += n[s] * static_cast<uint64_t>(g.w + (g.kind == kGroupString ? 4 : 0));
-        c->timed("set_build", (uni ? rowBytes[0] : 0) + rowBytes[1] + nBuild * 16, [&] {
-            if (uni && launchSetBuild(a, 0, c->stream)) throw Error{NGX_E_DEVICE, "set build"};
-            if (launchSetBuild(a, 1, c->stream)) throw Error{NGX_E_DEVICE, "set build"};
-        });
-        c->timed("set_probe", rowBytes[0] + (uni ? rowBytes[1] : 0) + (n[0] + (uni ? n[1] : 0)) * 16, [&] {
-            if (launchSetProbe(a, 0, c->stream)) throw Error{NGX_E_DEVICE, "set probe"};
-            if (uni && launchSetProbe(a, 1, c->stream)) throw Error{NGX_E_DEVICE, "set probe"};
-        });
-        SetState st{};
-        HIP_OK(hipMemcpyAsync(&st, a.S, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        c->setLoopFlushes += st.loopFlushes;
-        if (st.err || st.fill[0] > n[0] || st.fill[1] > n[1]) throw Error{NGX_E_DEVICE, "set op: inconsistent counts"};
-        if (st.fill[0] + st.fill[1] > static_cast<uint64_t>(c->setRowsMax)) return fail(c, NGX_E_UNSUPPORTED, "set op: output rows above set_rows_max");
-        // the kept rows of each side in that side's row order (MINUS / INTERSECT: left order; UNION DISTINCT: the
-        // left leaders, then the right ones)
-        for (int s = 0; s < 2; s++) {
-            kept[s].resize(st.fill[s]);
-            if (st.fill[s]) HIP_OK(hipMemcpyAsync(kept[s].data(), keepDev[s], st.fill[s] * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIP_OK(hipStreamSynchronize(c->stream));
-        for (int s = 0; s < 2; s++) {
-            std::sort(kept[s].begin(), kept[s].end());
-            if (!kept[s].empty()) HIP_OK(hipMemcpyAsync(keepDev[s], kept[s].data(), kept[s].size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        }
-        HIP_OK(hipStreamSynchronize(c->stream));                  // kept[] is pageable
-    }
-
-    // ---- emit: the left rows, then the right rows
-    const uint64_t mSide[2] = {pass < 0 ? kept[0].size() : pass == 0 ? n[0] : 0, pass < 0 ? kept[1].size() : pass == 1 ? n[1] : 0};
-    const uint64_t m = mSide[0] + mSide[1];
-    if (m == 0) {
-        HIP_OK(hipEventRecord(ev1, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        float ms0 = 0;
-        HIP_OK(hipEventElapsedTime(&ms0, ev0, ev1));
-        c->collectTimings();
-        R.r.device_ms = ms0;
-        c->setOpDevice++;
-        return NGX_OK;
-    }
-    GroupCell* cellsDev = c->sbCells.get<GroupCell>(m * ncols);
-    OrderEmitArgs ea[2] = {};
-    for (int s = 0; s < 2; s++) {
-        ea[s].n = n[s];
-        ea[s].m = mSide[s];
-        ea[s].rows = pass < 0 ? keepDev[s] : nullptr;
-        ea[s].ncols = ncols;
-        ea[s].cols = ecolsDev[s];
-        ea[s].cells = cellsDev + (s ? mSide[0] * ncols : 0);
-    }
-    uint64_t strBytes = 0;
-    if (anyString) {
-        uint64_t* slen = c->sbSlen.get<uint64_t>(m + 1);
-        uint64_t* spre = c->sbSpre.get<uint64_t>(m + 1);
-        uint64_t* tiles = c->sbTiles.get<uint64_t>((m + kTile - 1) / kTile + 1);
-        for (int s = 0; s < 2; s++)
-            if (launchOrderStrLen(ea[s], slen + (s ? mSide[0] : 0), c->stream)) throw Error{NGX_E_DEVICE, "set string lengths"};
-        if (launchScanU64(slen, m, spre, tiles, c->stream)) throw Error{NGX_E_DEVICE, "set string scan"};
-        strBytes = readScalar(c, spre + m);
-        char* strOut = c->sbStr.get<char>(std::max<uint64_t>(strBytes, 1));
-        for (int s = 0; s < 2; s++) {
-            ea[s].strPre = spre + (s ? mSide[0] : 0);             // one scan over both sides: one string block
-            ea[s].strOut = strOut;
-        }
-    }
-    c->timed("set_emit", m * ncols * sizeof(GroupCell) + strBytes, [&] {
-        for (int s = 0; s < 2; s++)
-            if (launchOrderEmit(ea[s], c->stream)) throw Error{NGX_E_DEVICE, "set emit"};
-    });
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    R.cells.resize(m * ncols);
-    HIP_OK(hipMemcpyAsync(R.cells.data(), cellsDev, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
-    R.strings.resize(strBytes);
-    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], ea[0].strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.r.device_ms = ms;
-    R.r.nrows = m;
-    R.r.cells = R.cells.data();
-    R.r.strings = R.strings.data();
-    R.r.strings_len = strBytes;
-    c->setOpDevice++;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_set_op(ngx_ctx* c, const ngx_go_result* left, const ngx_go_result* right, const ngx_set_plan* plan,
-                              ngx_set_result** out) {
-    if (!c || !left || !right || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<SetResultHolder>();
-    int32_t rc;
-    try {
-        rc = setOp(c, left, right, plan, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_set_result_free(ngx_set_result* r) {
-    if (r) delete reinterpret_cast<SetResultHolder*>(r);
-}
-
-// Both traversals with their results left in HBM, then ngx_set_op over them. A device-resident result is valid
-// until the next call on the context, so the right traversal runs on the second query lane (ngx_ctx::Lane: its
-// own scratch, result rows and reservation state, as ngx_go_batch rotates them) and with string arenas of its
-// own; the left result is not copied. The traversals run one after the other on the context's stream.
-extern "C" int32_t ngx_go_set(ngx_ctx* c, const ngx_go_plan* left, const ngx_go_plan* right, const ngx_set_plan* plan,
-                              ngx_set_result** out) {
-    if (!c || !left || !right || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<SetResultHolder>();
-    ngx_go_result *rl = nullptr, *rr = nullptr;
-    int32_t rc = NGX_OK;
-    if (!left->result_on_device || !right->result_on_device || left->distinct || right->distinct || left->input_vid_col ||
-        right->input_vid_col)
-        rc = fail(c, NGX_E_BAD_ARGUMENT, "set op: both plans are device-resident GOs without DISTINCT or input");
-    else if (c->world > 1)
-        rc = fail(c, NGX_E_UNSUPPORTED, "set op: world > 1 needs the shards' tables merged");
-    if (rc == NGX_OK) {
-        if (c->activeLane != 0) c->useLane(0);
-        rc = goCall(c, left, &rl);
-    }
-    if (rc == NGX_OK) {
-        uint64_t d0[3] = {0, 0, 0}, d1[3] = {0, 0, 0};
-        // string and untyped columns have no digest: the check covers integer / double / bool results
-        const bool check = c->setCheckLeft && rl->nrows && resultDigest(c, rl, d0) == NGX_OK;
-        c->useLane(1);
-        std::swap(c->strArena, c->setArena);
-        rc = goCall(c, right, &rr);
-        if (rc == NGX_OK && check) {
-            if (resultDigest(c, rl, d1) != NGX_OK || d0[0] != d1[0] || d0[1] != d1[1] || d0[2] != d1[2])
-                rc = fail(c, NGX_E_DEVICE, "set op: the left result changed during the right traversal");
-            else
-                c->setLeftChecks++;
-        }
-        if (rc == NGX_OK) {
-            try {
-                rc = setOp(c, rl, rr, plan, *R);
-            } catch (const Error& e) {
-                rc = fail(c, e.code, e.msg);
-            }
-        }
-        if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);
-        std::swap(c->strArena, c->setArena);
-        c->useLane(0);
-    }
-    const std::string err = c->lastError;
-    if (rr) ngx_go_result_free(rr);
-    if (rl) ngx_go_result_free(rl);
-    c->lastError = err;
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-// ------------------------------------------------------------------------ FETCH PROP ON (ngx_fetch, ngx_go_fetch)
-namespace {
-
-struct FetchResultHolder {
-    ngx_fetch_result r{};
-    std::vector<int32_t> colTypes;
-    std::vector<ngx_cell> cells;
-    std::string strings;
-};
-
-bool fetchIntType(int32_t t) { return t == NGX_T_INT || t == NGX_T_VID || t == NGX_T_TIMESTAMP; }
-
-// Every refusal and every prepare-time error is decided before the first launch.
-int32_t fetchOp(ngx_ctx* c, const ngx_go_result* r, const ngx_fetch_plan* p, FetchResultHolder& R) {
-    if (p->kind != NGX_FETCH_VERTEX && p->kind != NGX_FETCH_EDGE) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: unknown kind");
-    if (r && (r->code != NGX_OK || (r->nrows && r->ncols && !r->dev_cols))) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: not a device-resident result");
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "fetch: world > 1 needs the keys sent to their owners");
-    Space* spp = findSpace(c, p->space);
-    if (!spp || !spp->dev) return fail(c, NGX_E_NOT_LOADED, "space not committed");
-    const Space& sp = *spp;
-    const DeviceGraph& d = *sp.dev;
-    const bool edge = p->kind == NGX_FETCH_EDGE;
-    const int nkey = edge ? 3 : 1;
-    if (p->nyields < 0 || p->nyields + nkey > kFetchMaxCols) return fail(c, NGX_E_UNSUPPORTED, "fetch: more than 16 columns");
-    if (p->nyields && !p->yields) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: yields missing");
-    // ---- ON
-    std::vector<int32_t> tagSlot;
-    const SchemaSet* es = nullptr;
-    int32_t eslot = -1;
-    if (!edge) {
-        if (p->ntags == 0) return fail(c, NGX_E_UNSUPPORTED, "fetch: ON * (the column set depends on every tag of the space)");
-        if (p->ntags < 0 || !p->tags) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: tags missing");
-        if (p->ntags > kFetchMaxTags) return fail(c, NGX_E_UNSUPPORTED, "fetch: more than 8 tags");
-        for (int32_t t = 0; t < p->ntags; t++) {
-            const SchemaSet* ts = sp.tag(p->tags[t]);
-            if (!ts) return fail(c, NGX_E_QUERY, "Unknown error(406): ");               // Status::TagNotFound()
-            for (int32_t u = 0; u < t; u++)
-                if (p->tags[u] == p->tags[t]) return fail(c, NGX_E_QUERY, "tag(" + ts->name + ") was dup");
-            int32_t col;
-            int64_t dur;
-            if (ttlInfo(ts, col, dur)) return fail(c, NGX_E_UNSUPPORTED, "fetch: a TTL tag schema");
-            tagSlot.push_back(sp.tagSlotOf(p->tags[t]));
-        }
-    } else {
-        es = sp.edge(std::abs(p->edge_type));
-        if (!es || p->edge_type <= 0) return fail(c, NGX_E_QUERY, "Unknown error(407): ");  // Status::EdgeNotFound()
-        int32_t col;
-        int64_t dur;
-        if (ttlInfo(es, col, dur)) return fail(c, NGX_E_UNSUPPORTED, "fetch: a TTL edge schema");
-        eslot = sp.slotOf(p->edge_type);
-        if (eslot >= 0 && d.slots[eslot].hasFlags) return fail(c, NGX_E_UNSUPPORTED, "fetch: edges with empty or unreadable values");
-    }
-    if (edge && p->distinct && r) return fail(c, NGX_E_UNSUPPORTED, "fetch: DISTINCT over device-resident edge keys");
-    // ---- keys
-    const uint64_t n = r ? r->nrows : p->nkeys;
-    if (n >= (1ULL << 31)) return fail(c, NGX_E_UNSUPPORTED, "fetch: 2^31 keys or more");
-    const int nk = edge ? (p->key_cols[2] >= 0 ? 3 : 2) : 1;
-    const bool hasRank = edge && p->key_cols[2] >= 0;
-    auto inputCol = [&](int32_t col, GroupCol& g, int32_t& type, bool keyCol) -> int32_t {
-        if (!r) {                                                 // host keys: column k is key array k
-            if (col < 0 || col >= nk) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: input column out of range");
-            type = col == 2 ? NGX_T_INT : NGX_T_VID;
-            g = GroupCol{nullptr, nullptr, 0, 8, kGroupInt};
-            return NGX_OK;
-        }
-        if (col < 0 || col >= r->ncols) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: input column out of range");
-        type = r->col_types[col];
-        if (type == 0 || (r->nrows && r->dev_cols[col].type))
-            return fail(c, NGX_E_UNSUPPORTED, "fetch: UNKNOWN-typed column (per-row value types)");
-        if (keyCol && !fetchIntType(type)) return fail(c, NGX_E_UNSUPPORTED, "fetch: a non-integer key column");
-        const bool wide = type == NGX_T_STRING || type == NGX_T_DOUBLE || type == NGX_T_FLOAT;
-        g.kind = type == NGX_T_STRING ? kGroupString : wide ? kGroupDouble : kGroupInt;
-        g.w = wide ? 8 : r->dev_col_w ? r->dev_col_w[col] : 8;
-        g.konst = r->dev_col_const ? r->dev_col_const[col] : 0;
-        g.x = nullptr;
-        g.len = nullptr;
-        if (r->nrows) {
-            g.x = g.w ? r->dev_cols[col].x : nullptr;
-            g.len = r->dev_cols[col].len;
-            if (g.w && !g.x) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: column without values");
-            if (g.w != 0 && g.w != 1 && g.w != 2 && g.w != 4 && g.w != 8) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: column width");
-            if (type == NGX_T_STRING && !g.len) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: string column without lengths");
-        }
-        return NGX_OK;
-    };
-    FetchArgs a{};
-    int32_t keyType[3] = {NGX_T_VID, NGX_T_VID, NGX_T_INT};
-    for (int k = 0; k < nk; k++) {
-        int32_t t;
-        if (int32_t rc = inputCol(r ? p->key_cols[k] : k, a.key[k], t, true)) return rc;
-    }
-    if (!r && n) {
-        const int64_t* src[3] = {p->key_vid, p->key_dst, p->key_rank};
-        for (int k = 0; k < nk; k++)
-            if (!src[k]) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: key array missing");
-    }
-    // ---- yields
-    std::vector<FetchYield> ys(p->nyields);
-    R.colTypes.assign(keyType, keyType + nkey);
-    bool anyString = false;
-    for (int32_t y = 0; y < p->nyields; y++) {
-        const ngx_fetch_yield& q = p->yields[y];
-        FetchYield& f = ys[y];
-        f = FetchYield{};
-        int32_t type = NGX_T_INT;
-        if (q.kind == NGX_FY_TAG_PROP && !edge) {
-            int32_t t = 0;
-            while (t < p->ntags && p->tags[t] != q.tag) t++;
-            if (t == p->ntags) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: a yield's tag is not in ON");
-            const SchemaSet* ts = sp.tag(q.tag);
-            const std::string field = q.field ? q.field : "";
-            const int32_t fi = ts->latest().index(field);
-            if (fi < 0) return fail(c, NGX_E_QUERY, "`" + ts->name + "' is not a prop of `" + field + "'");
-            type = ts->latest().fields[fi].type;
-            f.src = kFyTagProp;
-            f.a = t;
-            if (tagSlot[t] >= 0) f.col = d.cols[d.tags[tagSlot[t]].colBase + fi];
-        } else if (q.kind == NGX_FY_EDGE_PROP && edge) {
-            const std::string field = q.field ? q.field : "";
-            const int32_t fi = es->latest().index(field);
-            if (fi < 0) return fail(c, NGX_E_QUERY, "`" + field + "' is not a prop of `" + es->name + "'");
-            type = es->latest().fields[fi].type;
-            f.src = kFyEdgeProp;
-            if (eslot >= 0) f.col = d.cols[d.slots[eslot].colBase + fi];
-        } else if (q.kind == NGX_FY_EDGE_KEY && edge) {
-            if (q.key < NGX_EK_SRC || q.key > NGX_EK_TYPE) return fail(c, NGX_E_BAD_ARGUMENT, "fetch: unknown key prop");
-            type = q.key <= NGX_EK_DST ? NGX_T_VID : NGX_T_INT;
-            f.src = q.key == NGX_EK_TYPE ? kFyEdgeType : kFyKey;
-            f.a = q.key;
-            f.konst = p->edge_type;
-        } else if (q.kind == NGX_FY_INPUT_COL) {
-            f.src = kFyInput;
-            if (int32_t rc = inputCol(q.col, f.in, type, false)) return rc;
-            f.a = q.col;
-        } else {
-            return fail(c, NGX_E_UNSUPPORTED, "fetch: a YIELD column that is no plain prop, key prop or input column");
-        }
-        if (type != NGX_T_BOOL && !fetchIntType(type) && type != NGX_T_FLOAT && type != NGX_T_DOUBLE && type != NGX_T_STRING)
-            return fail(c, NGX_E_UNSUPPORTED, "fetch: a column of an unknown type");
-        f.cell = type;                                            // NGX_CELL_* numbers its kinds as NGX_T_*
-        anyString |= type == NGX_T_STRING;
-        R.colTypes.push_back(type);
-    }
-    const int32_t ncols = nkey + p->nyields;
-    R.r.ncols = ncols;
-    R.r.col_types = R.colTypes.data();
-    R.r.input_rows = n;
-    if (n == 0) {                                                 // onEmptyInputs: the columns and no rows
-        c->fetchDevice++;
-        return NGX_OK;
-    }
-
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
-    if (!r) {
-        const int64_t* src[3] = {p->key_vid, p->key_dst, p->key_rank};
-        for (int k = 0; k < nk; k++) {
-            int64_t* dev = c->fxKeys[k].get<int64_t>(n);
-            HIP_OK(hipMemcpyAsync(dev, src[k], n * 8, hipMemcpyHostToDevice, c->stream));
-            a.key[k].x = dev;
-        }
-        for (FetchYield& f : ys)
-            if (f.src == kFyInput) f.in = a.key[f.a];
-    }
-    const uint64_t chunks = (n + 255) / 256;
-    a.n = n;
-    a.edge = edge ? 1 : 0;
-    a.nparts = sp.numParts;
-    a.hasRank = hasRank ? 1 : 0;
-    a.ntags = edge ? 0 : p->ntags;
-    a.vindex = d.vindex;
-    for (int32_t t = 0; t < a.ntags; t++) a.present[t] = tagSlot[t] >= 0 ? d.tags[tagSlot[t]].present : nullptr;
-    if (eslot >= 0) a.slot = d.slots[eslot];
-    a.keepMissing = !edge && p->keep_missing ? 1 : 0;
-    a.ny = p->nyields;
-    FetchYield* ysDev = c->fxDesc.get<FetchYield>(std::max<size_t>(ys.size(), 1));
-    if (!ys.empty()) HIP_OK(hipMemcpyAsync(ysDev, ys.data(), ys.size() * sizeof(FetchYield), hipMemcpyHostToDevice, c->stream));
-    a.ys = ysDev;
-    a.row = c->fxRow.get<uint32_t>(n);
-    a.eidx = c->fxEidx.get<uint64_t>(edge ? n : 1);
-    a.hits = c->fxHits.get<uint16_t>(n);
-    a.chunkCount = c->fxCount.get<uint64_t>(chunks + 1);
-    uint64_t* base = c->fxBase.get<uint64_t>(chunks + 1);
-    uint64_t* tiles = c->fxTiles.get<uint64_t>((chunks + kTile - 1) / kTile + 1);
-    a.chunkBase = base;
-    a.seen = c->fxSeen.get<uint32_t>(1);
-    a.gridMax = c->fetchGridMax;
-    HIP_OK(hipMemsetAsync(a.seen, 0, sizeof(uint32_t), c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));                      // ys and the host keys are pageable: copied before they go
-    uint64_t keyBytes = 0;
-    for (int k = 0; k < nk; k++) keyBytes += n * static_cast<uint64_t>(a.key[k].w);
-    c->timed("fetch_keys", keyBytes + n * (16 + 4 + 2 + (edge ? 8 : 0)), [&] {
-        if (launchFetchKeys(a, c->stream)) throw Error{NGX_E_DEVICE, "fetch keys"};
-    });
-    uint64_t m = 0;
-    c->timed("fetch_scan", chunks * 16, [&] {
-        if (launchScanU64(a.chunkCount, chunks, base, tiles, c->stream)) throw Error{NGX_E_DEVICE, "fetch scan"};
-    });
-    m = readScalar(c, base + chunks);
-    if (m > n) throw Error{NGX_E_DEVICE, "fetch: inconsistent counts"};
-    uint32_t seen = readScalar(c, a.seen);
-    R.r.tags_seen = seen;
-    if (m == 0) {
-        HIP_OK(hipEventRecord(ev1, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        float ms0 = 0;
-        HIP_OK(hipEventElapsedTime(&ms0, ev0, ev1));
-        c->collectTimings();
-        R.r.device_ms = ms0;
-        c->fetchDevice++;
-        return NGX_OK;
-    }
-    uint64_t strBytes = 0;
-    if (anyString) {
-        uint64_t* slen = c->fxSlen.get<uint64_t>(m + 1);
-        uint64_t* spre = c->fxSpre.get<uint64_t>(m + 1);
-        uint64_t* stiles = c->fxTiles.get<uint64_t>(std::max((m + kTile - 1) / kTile + 1, (chunks + kTile - 1) / kTile + 1));
-        a.lenOut = slen;
-        c->timed("fetch_emit", m * 8, [&] {
-            if (launchFetchEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "fetch string lengths"};
-        });
-        c->timed("fetch_scan", m * 16, [&] {
-            if (launchScanU64(slen, m, spre, stiles, c->stream)) throw Error{NGX_E_DEVICE, "fetch string scan"};
-        });
-        strBytes = readScalar(c, spre + m);
-        a.lenOut = nullptr;
-        a.strPre = spre;
-        a.strOut = c->fxStr.get<char>(std::max<uint64_t>(strBytes, 1));
-    }
-    a.cells = c->fxCells.get<GroupCell>(m * ncols);
-    c->timed("fetch_emit", m * ncols * sizeof(GroupCell) + strBytes, [&] {
-        if (launchFetchEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "fetch emit"};
-    });
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    R.cells.resize(m * ncols);
-    HIP_OK(hipMemcpyAsync(R.cells.data(), a.cells, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
-    R.strings.resize(strBytes);
-    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], a.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.r.device_ms = ms;
-    R.r.nrows = m;
-    R.r.cells = R.cells.data();
-    R.r.strings = R.strings.data();
-    R.r.strings_len = strBytes;
-    c->fetchDevice++;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_fetch(ngx_ctx* c, const ngx_go_result* r, const ngx_fetch_plan* plan, ngx_fetch_result** out) {
-    if (!c || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<FetchResultHolder>();
-    int32_t rc;
-    try {
-        rc = fetchOp(c, r, plan, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_fetch_result_free(ngx_fetch_result* r) {
-    if (r) delete reinterpret_cast<FetchResultHolder*>(r);
-}
-
-// The GO with its result left in HBM, then ngx_fetch over its columns, then the result freed: the traversal's rows
-// never cross to the host.
-extern "C" int32_t ngx_go_fetch(ngx_ctx* c, const ngx_go_plan* go, const ngx_fetch_plan* plan, ngx_fetch_result** out) {
-    if (!c || !go || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<FetchResultHolder>();
-    ngx_go_result* gr = nullptr;
-    int32_t rc = NGX_OK;
-    if (!go->result_on_device || go->distinct || go->input_vid_col)
-        rc = fail(c, NGX_E_BAD_ARGUMENT, "fetch: the plan is a device-resident GO without DISTINCT or input");
-    else if (c->world > 1)
-        rc = fail(c, NGX_E_UNSUPPORTED, "fetch: world > 1 needs the keys sent to their owners");
-    if (rc == NGX_OK) {
-        if (c->activeLane != 0) c->useLane(0);
-        rc = goCall(c, go, &gr);
-    }
-    if (rc == NGX_OK) {
-        try {
-            rc = fetchOp(c, gr, plan, *R);
-        } catch (const Error& e) {
-            rc = fail(c, e.code, e.msg);
-        }
-        if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);
-    }
-    const std::string err = c->lastError;
-    if (gr) ngx_go_result_free(gr);
-    c->lastError = err;
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-// ------------------------------------------------------------------------ LOOKUP ON (ngx_lookup)
-namespace {
-
-struct LookupResultHolder {
-    ngx_lookup_result r{};
-    std::vector<int32_t> colTypes;
-    std::vector<ngx_cell> cells;
-    std::string strings;
-};
-
-int32_t lookupKindOf(int32_t t) {
-    switch (t) {
-        case NGX_T_BOOL: return kLkBool;
-        case NGX_T_INT: case NGX_T_VID: case NGX_T_TIMESTAMP: return kLkInt;
-        case NGX_T_FLOAT: case NGX_T_DOUBLE: return kLkDouble;
-        case NGX_T_STRING: return kLkString;
-        default: return -1;
-    }
-}
-
-// Every refusal but one is decided before the first launch; an output above lookup_rows_max is known only after
-// the keep and scan passes and is refused before the emit. Nothing enumerates the Engine's rows on the host, so a
-// refusal is the caller's error: there is no host leg to fall back to (FETCH has one).
-// keep_bytes is the columns' stored widths times the rows scanned: an upper estimate for fixed-width columns (a row
-// rejected by an earlier condition does not read the later ones) and a lower one for a STRING condition, which
-// counts its two offsets' 8 bytes and not the string bytes compared.
-int32_t lookupOp(ngx_ctx* c, const ngx_lookup_plan* p, LookupResultHolder& R) {
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "lookup: world > 1 needs every shard's rows concatenated");
-    Space* spp = findSpace(c, p->space);
-    if (!spp || !spp->dev) return fail(c, NGX_E_NOT_LOADED, "space not committed");
-    const Space& sp = *spp;
-    const DeviceGraph& d = *sp.dev;
-    const bool edge = p->is_edge != 0;
-    const int nkey = edge ? 3 : 1;
-    if (p->nfields < 0 || p->nterms < 0 || p->nyields < 0) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: negative count");
-    if (p->nfields > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 scanned fields");
-    if (p->nterms > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 residual terms");
-    if (p->nyields + nkey > kLookupMax) return fail(c, NGX_E_UNSUPPORTED, "lookup: more than 16 columns");
-    if ((p->nfields && !p->fields) || (p->nterms && !p->terms) || (p->nyields && !p->yields))
-        return fail(c, NGX_E_BAD_ARGUMENT, "lookup: array missing");
-    const SchemaSet* ss = edge ? sp.edge(p->schema_id) : sp.tag(p->schema_id);
-    if (!ss || (edge && p->schema_id <= 0)) return fail(c, NGX_E_QUERY, edge ? "Unknown error(407): " : "Unknown error(406): ");
-    int32_t tcol;
-    int64_t tdur;
-    if (ttlInfo(ss, tcol, tdur)) return fail(c, NGX_E_UNSUPPORTED, edge ? "lookup: a TTL edge schema" : "lookup: a TTL tag schema");
-    const int32_t slot = edge ? sp.slotOf(p->schema_id) : sp.tagSlotOf(p->schema_id);
-    if (edge && slot >= 0 && d.slots[slot].hasFlags) return fail(c, NGX_E_UNSUPPORTED, "lookup: edges with empty or unreadable values");
-    const int32_t colBase = slot < 0 ? 0 : edge ? d.slots[slot].colBase : d.tags[slot].colBase;
-    auto column = [&](const char* name, DCol& col, int32_t& type) -> int32_t {
-        const std::string field = name ? name : "";
-        const int32_t fi = ss->latest().index(field);
-        if (fi < 0) return fail(c, NGX_E_QUERY, "Unknown column `" + field + "' in schema");
-        type = ss->latest().fields[fi].type;
-        if (lookupKindOf(type) < 0) return fail(c, NGX_E_UNSUPPORTED, "lookup: a column of an unknown type");
-        col = DCol{};
-        if (slot >= 0) {
-            col = d.cols[colBase + fi];
-            if (col.valid) return fail(c, NGX_E_UNSUPPORTED, "lookup: field `" + field + "' is missing from some row's schema version");
-        }
-        return NGX_OK;
-    };
-    std::vector<LookupCond> conds(p->nfields + p->nterms);
-    std::string pool;
-    uint64_t rowBytes = edge ? 0 : 1;                             // present[]
-    for (int32_t i = 0; i < p->nfields + p->nterms; i++) {
-        const bool term = i >= p->nfields;
-        const ngx_lookup_cond& q = term ? p->terms[i - p->nfields] : p->fields[i];
-        LookupCond& k = conds[i];
-        k = LookupCond{};
-        int32_t type;
-        if (int32_t rc = column(q.field, k.col, type)) return rc;
-        k.kind = lookupKindOf(type);
-        if (q.kind < NGX_LK_INT || q.kind > NGX_LK_STRING) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: unknown constant kind");
-        k.ckind = q.kind;
-        k.op = q.op;
-        if (term) {
-            if (q.op < kLkLT || q.op > kLkNE) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: unknown operator");
-            k.lo = static_cast<uint64_t>(q.kind == NGX_LK_BOOL ? (q.bits ? 1 : 0) : q.bits);
-        } else {
-            if (q.kind != k.kind) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: a scanned field's constant is not of the field's type");
-            k.lo = k.kind == kLkBool ? (q.bits ? 1 : 0) : q.lo;
-            k.hi = q.hi;
-        }
-        if (q.kind == NGX_LK_STRING) {
-            if (q.str_len >= (1ULL << 31) || (q.str_len && !q.str)) return fail(c, NGX_E_BAD_ARGUMENT, "lookup: string constant");
-            k.soff = pool.size();
-            k.slen = static_cast<int32_t>(q.str_len);
-            pool.append(q.str ? q.str : "", q.str_len);
-        }
-        rowBytes += k.kind == kLkInt ? k.col.width : k.kind == kLkBool ? 1 : 8;
-    }
-    std::vector<LookupYield> ys(p->nyields);
-    static const int32_t keyTypeV[1] = {NGX_T_VID}, keyTypeE[3] = {NGX_T_VID, NGX_T_VID, NGX_T_INT};
-    R.colTypes.assign(edge ? keyTypeE : keyTypeV, (edge ? keyTypeE : keyTypeV) + nkey);
-    bool anyString = false;
-    for (int32_t y = 0; y < p->nyields; y++) {
-        int32_t type;
-        ys[y] = LookupYield{};
-        if (int32_t rc = column(p->yields[y], ys[y].col, type)) return rc;
-        ys[y].cell = type;                                        // NGX_CELL_* numbers its kinds as NGX_T_*
-        anyString |= type == NGX_T_STRING;
-        R.colTypes.push_back(type);
-    }
-    const int32_t ncols = nkey + p->nyields;
-    R.r.ncols = ncols;
-    R.r.col_types = R.colTypes.data();
-    HIP_OK(hipSetDevice(c->device));
-    uint64_t n = 0;
-    if (slot >= 0) n = edge ? (d.V ? readScalar(c, d.slots[slot].off + d.V) : 0) : d.V;
-    R.r.scanned_rows = n;
-    R.r.keep_bytes = n * rowBytes;
-    if (n == 0) {                                                 // no row of the tag / no edge of the type
-        c->lookupDevice++;
-        return NGX_OK;
-    }
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
-    LookupArgs a{};
-    a.n = n;
-    a.V = d.V;
-    a.edge = edge ? 1 : 0;
-    a.nf = p->nfields;
-    a.nt = p->nterms;
-    a.ny = p->nyields;
-    a.vid = d.vid;
-    if (edge) a.slot = d.slots[slot];
-    else a.present = d.tags[slot].present;
-    LookupCond* condsDev = c->lkConds.get<LookupCond>(std::max<size_t>(conds.size(), 1));
-    if (!conds.empty()) HIP_OK(hipMemcpyAsync(condsDev, conds.data(), conds.size() * sizeof(LookupCond), hipMemcpyHostToDevice, c->stream));
-    char* poolDev = c->lkPool.get<char>(std::max<size_t>(pool.size(), 1));
-    if (!pool.empty()) HIP_OK(hipMemcpyAsync(poolDev, pool.data(), pool.size(), hipMemcpyHostToDevice, c->stream));
-    LookupYield* ysDev = c->lkYs.get<LookupYield>(std::max<size_t>(ys.size(), 1));
-    if (!ys.empty()) HIP_OK(hipMemcpyAsync(ysDev, ys.data(), ys.size() * sizeof(LookupYield), hipMemcpyHostToDevice, c->stream));
-    a.conds = condsDev;
-    a.pool = poolDev;
-    a.ys = ysDev;
-    const uint64_t chunks = (n + 255) / 256;
-    a.keep = c->lkKeep.get<uint8_t>(n);
-    a.chunkCount = c->lkCount.get<uint64_t>(chunks + 1);
-    uint64_t* base = c->lkBase.get<uint64_t>(chunks + 1);
-    uint64_t* tiles = c->lkTiles.get<uint64_t>((chunks + kTile - 1) / kTile + 1);
-    a.chunkBase = base;
-    a.gridMax = c->lookupGridMax;
-    HIP_OK(hipStreamSynchronize(c->stream));                      // the descriptors are pageable: copied before they go
-    c->timed("lookup_keep", n * rowBytes + n, [&] {
-        if (launchLookupKeep(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup keep"};
-    });
-    c->timed("lookup_scan", chunks * 16, [&] {
-        if (launchScanU64(a.chunkCount, chunks, base, tiles, c->stream)) throw Error{NGX_E_DEVICE, "lookup scan"};
-    });
-    const uint64_t m = readScalar(c, base + chunks);
-    if (m > n) throw Error{NGX_E_DEVICE, "lookup: inconsistent counts"};
-    if (m > static_cast<uint64_t>(c->lookupRowsMax))
-        return fail(c, NGX_E_UNSUPPORTED, "lookup: " + std::to_string(m) + " rows, above lookup_rows_max");
-    uint64_t strBytes = 0;
-    if (m) {
-        if (anyString) {
-            uint64_t* slen = c->lkSlen.get<uint64_t>(m + 1);
-            uint64_t* spre = c->lkSpre.get<uint64_t>(m + 1);
-            uint64_t* stiles = c->lkTiles.get<uint64_t>(std::max((m + kTile - 1) / kTile + 1, (chunks + kTile - 1) / kTile + 1));
-            a.lenOut = slen;
-            c->timed("lookup_emit", m * 8, [&] {
-                if (launchLookupEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup string lengths"};
-            });
-            c->timed("lookup_scan", m * 16, [&] {
-                if (launchScanU64(slen, m, spre, stiles, c->stream)) throw Error{NGX_E_DEVICE, "lookup string scan"};
-            });
-            strBytes = readScalar(c, spre + m);
-            a.lenOut = nullptr;
-            a.strPre = spre;
-            a.strOut = c->lkStr.get<char>(std::max<uint64_t>(strBytes, 1));
-        }
-        a.cells = c->lkCells.get<GroupCell>(m * ncols);
-        c->timed("lookup_emit", n + m * ncols * sizeof(GroupCell) + strBytes, [&] {
-            if (launchLookupEmit(a, c->stream)) throw Error{NGX_E_DEVICE, "lookup emit"};
-        });
-    }
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    R.cells.resize(m * ncols);
-    if (m) HIP_OK(hipMemcpyAsync(R.cells.data(), a.cells, R.cells.size() * sizeof(ngx_cell), hipMemcpyDeviceToHost, c->stream));
-    R.strings.resize(strBytes);
-    if (strBytes) HIP_OK(hipMemcpyAsync(&R.strings[0], a.strOut, strBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.r.device_ms = ms;
-    R.r.nrows = m;
-    R.r.cells = R.cells.data();
-    R.r.strings = R.strings.data();
-    R.r.strings_len = strBytes;
-    c->lookupDevice++;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_lookup(ngx_ctx* c, const ngx_lookup_plan* plan, ngx_lookup_result** out) {
-    if (!c || !plan || !out) return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<LookupResultHolder>();
-    int32_t rc;
-    try {
-        rc = lookupOp(c, plan, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left reading the descriptors
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_lookup_result_free(ngx_lookup_result* r) {
-    if (r) delete reinterpret_cast<LookupResultHolder*>(r);
-}
-
-// ------------------------------------------------------------------------ FIND SHORTEST PATH (ngx_find_path)
-namespace {
-
-struct PathResultHolder {
-    ngx_path_result r{};
-    std::vector<std::string> names;
-    std::vector<const char*> cnames;
-    std::vector<int32_t> types, etype;
-    std::vector<int64_t> src, dst, rank;
-    std::vector<uint64_t> mask;
-};
-
-// one side's levels: device lists of (row, bits) and their sizes
-struct PathLevels {
-    std::vector<const uint32_t*> rows;
-    std::vector<const uint64_t*> masks;
-    std::vector<uint64_t> n;
-};
-
-int32_t findPath(ngx_ctx* c, const ngx_path_plan& p, PathResultHolder& R) {
-    if (p.kind != NGX_PATH_SHORTEST) return fail(c, NGX_E_UNSUPPORTED, "find path: ALL and NOLOOP enumerate walks, not levels");
-    if (p.direction != NGX_DIR_FORWARD && p.direction != NGX_DIR_REVERSELY) return fail(c, NGX_E_UNSUPPORTED, "find path: BIDIRECT");
-    if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "find path: world > 1 needs the levels exchanged");
-    if (p.upto < 1 || p.upto > 500) return fail(c, NGX_E_UNSUPPORTED, "find path: UPTO outside 1 .. 500");
-    Space* spp = findSpace(c, p.space);
-    if (!spp || !spp->dev) return fail(c, NGX_E_NOT_LOADED, "space not committed");
-    const Space& sp = *spp;
-    const DeviceGraph& d = *sp.dev;
-    if (c->maxEdgesPerVertex < INT32_MAX) return fail(c, NGX_E_UNSUPPORTED, "find path: max_edge_returned_per_vertex is set");
-    std::vector<int32_t> over;
-    if (p.over_all) {
-        for (auto& name : sp.edgeOrder) { R.names.push_back(name); over.push_back(sp.edgeByName.at(name)); }
-    } else {
-        for (int32_t i = 0; i < p.nover; i++) {
-            const std::string name = p.over_names[i];
-            auto it = sp.edgeByName.find(name);
-            if (it == sp.edgeByName.end()) return fail(c, NGX_E_QUERY, "Edge `" + name + "' not found");
-            if (std::find(over.begin(), over.end(), it->second) != over.end()) return fail(c, NGX_E_UNSUPPORTED, "find path: an edge listed twice");
-            R.names.push_back(name);
-            over.push_back(it->second);
-        }
-    }
-    R.types = over;
-    for (auto& n : R.names) R.cnames.push_back(n.c_str());
-    R.r.nedge_names = static_cast<int32_t>(over.size());
-    R.r.edge_names = R.cnames.data();
-    R.r.edge_types = R.types.data();
-    for (int32_t t : over) {
-        int32_t col;
-        int64_t dur;
-        if (ttlInfo(sp.edge(std::abs(t)), col, dur)) return fail(c, NGX_E_UNSUPPORTED, "find path: a TTL edge schema");
-    }
-    const uint64_t nS = p.nfrom, nT = p.nto;
-    {
-        std::unordered_set<int64_t> fs, ts;
-        for (uint64_t i = 0; i < nS; i++) if (!fs.insert(p.from[i]).second) return fail(c, NGX_E_UNSUPPORTED, "find path: a vid listed twice");
-        for (uint64_t i = 0; i < nT; i++) if (!ts.insert(p.to[i]).second) return fail(c, NGX_E_UNSUPPORTED, "find path: a vid listed twice");
-        if (nT > 64) return fail(c, NGX_E_UNSUPPORTED, "find path: more than 64 targets");
-        for (uint64_t i = 0; i < nS; i++) if (ts.count(p.from[i])) return fail(c, NGX_E_UNSUPPORTED, "find path: a vertex on both sides");
-    }
-    if (nS == 0 || nT == 0) {                                     // getNeighborsAndFindPath: a dead end finishes
-        c->findPathDevice++;
-        return NGX_OK;
-    }
-    if (nS >= (1ULL << 31)) return fail(c, NGX_E_UNSUPPORTED, "find path: 2^31 sources or more");
-    std::vector<int32_t> typesSide[2], hopTypes;
-    for (int32_t t : over) {
-        typesSide[0].push_back(p.direction == NGX_DIR_FORWARD ? t : -t);
-        typesSide[1].push_back(p.direction == NGX_DIR_FORWARD ? -t : t);
-    }
-    HopSlots hs[2];
-    for (int side = 0; side < 2; side++) {
-        hs[side] = makeHopSlots(sp, d, typesSide[side], hopTypes);
-        for (int s = 0; s < hs[side].n; s++)
-            if (hs[side].eflags[s]) return fail(c, NGX_E_UNSUPPORTED, "find path: edges with empty or unreadable values");
-    }
-
-    HIP_OK(hipSetDevice(c->device));
-    for (hipEvent_t& e : c->gbEv)
-        if (!e) HIP_OK(hipEventCreate(&e));
-    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
-    HIP_OK(hipEventRecord(ev0, c->stream));
-    const uint64_t G = std::max<uint64_t>(d.vglobal, 1);
-    uint64_t *inc[2], *seen[2], *newD[2] = {nullptr, nullptr}, *keep[3];
-    uint8_t* lvl[2];
-    uint32_t* touched[2];
-    for (int side = 0; side < 2; side++) {
-        inc[side] = c->fpInc[side].get<uint64_t>(G);
-        seen[side] = c->fpSeen[side].get<uint64_t>(G);
-        lvl[side] = c->fpLvl[side].get<uint8_t>(G);
-        touched[side] = c->fpTouched[side].get<uint32_t>(G);
-        HIP_OK(hipMemsetAsync(inc[side], 0, G * 8, c->stream));
-        HIP_OK(hipMemsetAsync(seen[side], 0, G * 8, c->stream));
-        HIP_OK(hipMemsetAsync(lvl[side], 0xFF, G, c->stream));
-    }
-    newD[1] = c->fpNew.get<uint64_t>(G);
-    for (int k = 0; k < 3; k++) {
-        keep[k] = c->fpKeep[k].get<uint64_t>(G);
-        HIP_OK(hipMemsetAsync(keep[k], 0, G * 8, c->stream));
-    }
-    const uint64_t cap = static_cast<uint64_t>(c->pathRowsMax);
-    PathEdge* outDev = c->fpOut.get<PathEdge>(cap);
-    PathState* S = c->fpState.get<PathState>(1);
-    HIP_OK(hipMemsetAsync(S, 0, sizeof(PathState), c->stream));
-
-    // ---- level 0: the vids' rows (a vid without a vertex has none and takes no part)
-    PathLevels lv[2];
-    auto levelBufs = [&](int side, size_t level, uint64_t n, uint32_t*& rows, uint64_t*& masks) {
-        if (c->fpRows[side].size() <= level) { c->fpRows[side].resize(level + 1); c->fpMasks[side].resize(level + 1); }
-        rows = c->fpRows[side][level].get<uint32_t>(std::max<uint64_t>(n, 1));
-        masks = c->fpMasks[side][level].get<uint64_t>(std::max<uint64_t>(n, 1));
-    };
-    {
-        std::vector<int32_t> parts;
-        std::vector<int64_t> vids(p.from, p.from + nS);
-        vids.insert(vids.end(), p.to, p.to + nT);
-        for (int64_t v : vids) parts.push_back(idHash(v, sp.numParts));
-        const uint64_t n = vids.size();
-        int64_t* dv = c->seedVid.get<int64_t>(n * 2);             // vids, then parts
-        int32_t* dpart = reinterpret_cast<int32_t*>(dv + n);
-        stageSeeds(c, parts, vids, dpart, dv);
-        uint32_t* rowsIn = c->fpSeed.get<uint32_t>(n);
-        if (launchIndexLookup(dpart, dv, n, d.vindex, rowsIn, c->stream)) throw Error{NGX_E_DEVICE, "lookup"};
-        for (int side = 0; side < 2; side++) {
-            uint32_t* rows;
-            uint64_t* masks;
-            levelBufs(side, 0, side ? nT : nS, rows, masks);
-            if (launchPathSeed(rowsIn + (side ? nS : 0), side ? nT : nS, side, seen[side], newD[side], lvl[side], rows, masks,
-                               &S->nLevel[side], c->stream))
-                throw Error{NGX_E_DEVICE, "path seed"};
-            lv[side].rows.push_back(rows);
-            lv[side].masks.push_back(masks);
-        }
-    }
-    PathState st{};
-    auto readState = [&] {
-        HIP_OK(hipMemcpyAsync(&st, S, sizeof st, hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (st.err) throw Error{NGX_E_DEVICE, "find path: inconsistent counts"};
-    };
-    readState();
-    lv[0].n.push_back(st.nLevel[0]);
-    lv[1].n.push_back(st.nLevel[1]);
-
-    // keep masks: [0] the from side's seeds, [1] the to side's, [2] the spare; all zero between sweeps
-    auto sweepSide = [&](int side, int level, int cur) {
-        int next = 2;
-        for (int j = level - 1; j >= 0; j--) {
-            PathSweepArgs a{};
-            a.rows = lv[side].rows[j];
-            a.masks = side ? lv[side].masks[j] : nullptr;
-            a.n = lv[side].n[j];
-            a.hs = hs[side];
-            a.vid = d.vid;
-            a.keepCur = keep[cur];
-            a.keepNext = keep[next];
-            a.out = outDev;
-            a.cap = cap;
-            a.S = S;
-            a.reverse = side;
-            a.gridMax = c->pathGridMax;
-            c->timed("path_sweep", 0, [&] {
-                if (launchPathSweep(a, false, c->stream)) throw Error{NGX_E_DEVICE, "path sweep"};
-                if (launchPathClear(lv[side].rows[j + 1], lv[side].n[j + 1], keep[cur], c->stream)) throw Error{NGX_E_DEVICE, "path clear"};
-            });
-            std::swap(cur, next);
-        }
-        // level 0's keep masks go too: all three arrays are zero again
-        if (launchPathClear(lv[side].rows[0], lv[side].n[0], keep[cur], c->stream)) throw Error{NGX_E_DEVICE, "path clear"};
-    };
-    const uint64_t all = nT == 64 ? ~0ULL : (1ULL << nT) - 1;
-    const uint32_t steps = p.upto / 2 + p.upto % 2;
-    uint64_t found = 0;
-    int32_t levels = 0;
-    bool tooMany = false;
-    for (uint32_t k = 1; k <= steps && !tooMany; k++) {
-        if (lv[0].n[k - 1] == 0 || lv[1].n[k - 1] == 0) break;    // a side without vids ends the search
-        const bool even = 2ULL * k <= p.upto;                     // an even path of 2k edges is within UPTO
-        HIP_OK(hipMemsetAsync(S, 0, offsetof(PathState, edges), c->stream));
-        // odd meet: level k - 1 of the from side over its edges into level k - 1 of the to side (2k - 2 <= UPTO holds)
-        {
-            PathSweepArgs a{};
-            a.rows = lv[0].rows[k - 1];
-            a.n = lv[0].n[k - 1];
-            a.hs = hs[0];
-            a.vid = d.vid;
-            a.keepNext = keep[0];
-            a.tLvl = lvl[1];
-            a.tNew = newD[1];
-            a.keepT = keep[1];
-            a.notFound = all & ~found;
-            a.level = static_cast<uint8_t>(k - 1);
-            a.out = outDev;
-            a.cap = cap;
-            a.S = S;
-            a.gridMax = c->pathGridMax;
-            c->timed("path_meet", 0, [&] { if (launchPathSweep(a, true, c->stream)) throw Error{NGX_E_DEVICE, "path meet"}; });
-        }
-        readState();                                              // the odd meet's targets: they may end the search
-        if (st.edges > cap) { tooMany = true; break; }
-        if (st.found[0]) {
-            found |= st.found[0];
-            sweepSide(0, static_cast<int>(k) - 1, 0);
-            sweepSide(1, static_cast<int>(k) - 1, 1);
-        }
-        if (found == all || !even) break;
-        c->timed("path_expand", 0, [&] {
-            for (int side = 0; side < 2; side++)
-                if (launchPathExpand(lv[side].rows[k - 1], side ? lv[side].masks[k - 1] : nullptr, lv[side].n[k - 1], hs[side], inc[side],
-                                     touched[side], G, S, side, c->stream))
-                    throw Error{NGX_E_DEVICE, "path expand"};
-        });
-        levels += 2;
-        readState();                                              // the rows the expansions reached: they size the new levels
-        if (st.edges > cap) { tooMany = true; break; }
-        uint32_t* rows[2];
-        uint64_t* masks[2];
-        c->timed("path_settle", 0, [&] {
-            for (int side = 0; side < 2; side++) {
-                levelBufs(side, k, st.touched[side], rows[side], masks[side]);
-                if (launchPathSettle(touched[side], st.touched[side], inc[side], seen[side], newD[side], lvl[side], static_cast<uint8_t>(k),
-                                     rows[side], masks[side], S, side, c->stream))
-                    throw Error{NGX_E_DEVICE, "path settle"};
-                lv[side].rows.push_back(rows[side]);
-                lv[side].masks.push_back(masks[side]);
-            }
-        });
-        c->timed("path_meet", 0, [&] {
-            if (launchPathMeetEven(rows[1], masks[1], st.touched[1], lvl[0], static_cast<uint8_t>(k), found, keep[0], keep[1], S, c->stream))
-                throw Error{NGX_E_DEVICE, "path meet"};
-        });
-        readState();                                              // the new levels' sizes, the even meet's targets
-        lv[0].n.push_back(st.nLevel[0]);
-        lv[1].n.push_back(st.nLevel[1]);
-        if (st.found[1]) {
-            found |= st.found[1];
-            sweepSide(0, static_cast<int>(k), 0);
-            sweepSide(1, static_cast<int>(k), 1);
-        }
-        if (found == all) break;
-    }
-    if (!tooMany) {
-        readState();                                              // the last sweeps' edges
-        tooMany = st.edges > cap;
-    }
-    c->findPathLoopFlushes += st.loopFlushes;
-    if (tooMany) {
-        c->collectTimings();
-        return fail(c, NGX_E_UNSUPPORTED, "find path: path edges above path_rows_max");
-    }
-    HIP_OK(hipEventRecord(ev1, c->stream));
-    const uint64_t m = st.edges;
-    std::vector<PathEdge> host(m);
-    if (m) HIP_OK(hipMemcpyAsync(host.data(), outDev, m * sizeof(PathEdge), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
-    c->collectTimings();
-    R.src.resize(m); R.dst.resize(m); R.rank.resize(m); R.etype.resize(m); R.mask.resize(m);
-    for (uint64_t i = 0; i < m; i++) {
-        R.src[i] = host[i].src; R.dst[i] = host[i].dst; R.rank[i] = host[i].rank; R.etype[i] = host[i].type; R.mask[i] = host[i].mask;
-    }
-    R.r.nedges = m;
-    R.r.src = R.src.data(); R.r.dst = R.dst.data(); R.r.rank = R.rank.data(); R.r.type = R.etype.data(); R.r.mask = R.mask.data();
-    R.r.found = found;
-    R.r.levels = levels;
-    R.r.device_ms = ms;
-    c->findPathDevice++;
-    c->findPathLevels += static_cast<uint64_t>(levels);
-    c->findPathEdges += m;
-    return NGX_OK;
-}
-
-}  // namespace
-
-extern "C" int32_t ngx_find_path(ngx_ctx* c, const ngx_path_plan* plan, ngx_path_result** out) {
-    if (!c || !plan || !out || (plan->nfrom && !plan->from) || (plan->nto && !plan->to) || (plan->nover && !plan->over_names))
-        return NGX_E_BAD_ARGUMENT;
-    std::lock_guard<std::mutex> g(c->mu);
-    auto R = std::make_unique<PathResultHolder>();
-    int32_t rc;
-    try {
-        if (c->activeLane != 0) c->useLane(0);
-        rc = findPath(c, *plan, *R);
-    } catch (const Error& e) {
-        rc = fail(c, e.code, e.msg);
-    }
-    if (rc != NGX_OK) (void)hipStreamSynchronize(c->stream);     // no kernel left writing the scratch
-    R->r.code = rc;
-    *out = &R.release()->r;
-    return rc;
-}
-
-extern "C" void ngx_path_result_free(ngx_path_result* r) {
-    if (r) delete reinterpret_cast<PathResultHolder*>(r);
-}

@@ -110,7 +110,7 @@ struct StagedRows {
     std::vector<uint64_t> voff;         // n + 1
 };
 
-struct DeviceGraph;                     // engine.cpp
+struct DeviceGraph;                     // engine_ctx.h
 
 struct Space {
     int32_t id = 0;

@@ -1,4 +1,4 @@
-"""The path DAG of ngx_find_path (nebula_amd/csrc/findpath.hip, engine.cpp::findPath) against the breadth-first model
+"""The path DAG of ngx_find_path (nebula_amd/csrc/findpath.hip, op_findpath.cpp::findPath) against the breadth-first model
 of tests/pathref.py, edge by edge and target bit by target bit, with the found mask and the levels expanded.
 
 Every case calls Engine.find_path(..., rows=False), checks that the stat find_path_device rose by one, and compares

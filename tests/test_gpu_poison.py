@@ -1,7 +1,7 @@
 """Every word a kernel reads was written by a kernel of the same query.
 
 The engine flag poison_buffers fills every device scratch buffer allocated from then on with 0xA5
-bytes (engine.cpp DBuf). Without it a fresh process's allocations are often zero and later ones hold
+bytes (engine_ctx.h DBuf). Without it a fresh process's allocations are often zero and later ones hold
 an earlier query's values, which can hide a kernel reading a word nothing wrote: the wire-row encoder
 (k_encode_rows) did fault once on exactly that. With the poison:
 

@@ -22,7 +22,7 @@
 #include "../../nebula_amd/csrc/ngx_internal.h"
 
 namespace ngx {
-struct DeviceGraph {};                      // engine.cpp's is not linked: Space only holds the pointer
+struct DeviceGraph {};                      // engine_ctx.h's is not linked: Space only holds the pointer
 }
 
 extern "C" {
