@@ -788,7 +788,20 @@ void ngx_lookup_result_free(ngx_lookup_result* r);
  * last are refused before any level is expanded.
  * Flags (read-only): "find_path_device" calls answered on the device, "find_path_levels" levels expanded and
  * "find_path_edges" path-DAG edges returned by them, "find_path_loop_flushes" LDS buffer flushes inside a sweep's
- * edge loop. ngx_kernel_stats: launch groups "path_expand", "path_settle", "path_meet", "path_sweep". */
+ * edge loop. ngx_kernel_stats: launch groups "path_expand", "path_settle", "path_meet", "path_sweep".
+ *
+ * FIND ALL PATH and FIND NOLOOP PATH, behind flag "find_path_all" (0 / 1, default 0: refused as above). ALL returns
+ * every walk of 1 .. upto edges from a source to a target, each once, vertices and edges repeated at will; NOLOOP
+ * those of them whose vertices are all distinct. The answer is a layered edge set, not the walks: the
+ * to side's levels run to depth upto - 1 and keep per depth d and row the targets within d edges; then one launch
+ * per layer i = 0 .. upto - 1 of the from side, layer 0 being the sources' rows, emits every edge u -> v of a layer
+ * row u with m = the targets within upto - 1 - i edges of v != 0, and lists v once in layer i + 1. `layer` holds i,
+ * `mask` m; each (layer, edge) pair occurs once. `found` has bit j iff an emitted edge ends at to[j]; `levels` is the
+ * to side's depths expanded plus the from side's layers launched. The walks are every path that starts at a source
+ * in layer 0, follows only edges of its current layer and stands on a target after at least one edge
+ * (nebula_amd/findpath.py paths_from_layers, which drops NOLOOP's revisits). Refused as SHORTEST is, and for upto
+ * above 8 (before any launch); more emitted edges than "path_rows_max" is known after the layers have run.
+ * Flag (read-only) "find_path_layers": from-side layers launched. ngx_kernel_stats: launch group "path_walk". */
 #define NGX_PATH_SHORTEST 0
 #define NGX_PATH_ALL 1
 #define NGX_PATH_NOLOOP 2
@@ -819,6 +832,7 @@ typedef struct {
     uint64_t found;                    /* bit j: to[j] was reached */
     int32_t levels;                    /* levels expanded, both sides */
     double device_ms;                  /* HIP-event time, first clear to the last edge */
+    const uint8_t* layer;              /* ALL / NOLOOP: per edge the step of a walk it is, from 0; SHORTEST: NULL */
 } ngx_path_result;
 int32_t ngx_find_path(ngx_ctx* ctx, const ngx_path_plan* plan, ngx_path_result** out);
 void ngx_path_result_free(ngx_path_result* r);

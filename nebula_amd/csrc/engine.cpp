@@ -1674,6 +1674,11 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
         c->pathRowsMax = value;
         return NGX_OK;
     }
+    if (n == "find_path_all") {
+        if (value != 0 && value != 1) return fail(c, NGX_E_BAD_ARGUMENT, "find_path_all: 0 or 1");
+        c->findPathAll = value == 1;
+        return NGX_OK;
+    }
     if (n == "path_grid_max") {
         if (value < 0 || value > static_cast<int64_t>(kPathGridMax))
             return fail(c, NGX_E_BAD_ARGUMENT, "path_grid_max: 0 (built-in) or 1 .. " + std::to_string(kPathGridMax));
@@ -1751,6 +1756,8 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "find_path_levels") *value = static_cast<int64_t>(c->findPathLevels);
     else if (n == "find_path_edges") *value = static_cast<int64_t>(c->findPathEdges);
     else if (n == "find_path_loop_flushes") *value = static_cast<int64_t>(c->findPathLoopFlushes);
+    else if (n == "find_path_all") *value = c->findPathAll ? 1 : 0;
+    else if (n == "find_path_layers") *value = static_cast<int64_t>(c->findPathLayers);
     else if (n == "set_check_left") *value = c->setCheckLeft ? 1 : 0;
     else if (n == "set_left_checks") *value = static_cast<int64_t>(c->setLeftChecks);
     else if (n == "set_grid_max") *value = c->setGridMax;

@@ -328,6 +328,10 @@ struct ngx_ctx : LaneState {
     int64_t pathRowsMax = int64_t(1) << 20;             // flag path_rows_max: the most path-DAG edges answered on the device
     uint32_t pathGridMax = 0;                           // flag path_grid_max: most workgroups of a sweep, 0: built-in
     uint64_t findPathDevice = 0, findPathLevels = 0, findPathEdges = 0, findPathLoopFlushes = 0;
+    // FIND ALL / NOLOOP PATH: the to side's seen words after each depth (UPTO per row), the layer that listed a row last
+    DBuf fpCum, fpStamp;
+    bool findPathAll = false;                           // flag find_path_all: ngx_find_path answers ALL and NOLOOP too
+    uint64_t findPathLayers = 0;                        // flag find_path_layers: from-side layers launched for them
     DBuf pullGather;                                    // world > 1 pull: all shards' frontier bitmaps
     struct { int64_t qps = 0, errorQps = 0, latencySum = 0, latencyCount = 0, latencyMax = 0; } gbStats;
     std::vector<ngx_stat> statList;                     // ngx_stats view

@@ -16,6 +16,14 @@
 //            for those bits, and they join the row's keep mask. Edges collect in LDS and leave a buffer at a time:
 //            one atomicAdd reserves the buffer's place in the output (as k_order_collect / k_set_probe).
 // Every hand-off between these steps is a kernel boundary on one stream.
+//
+// FIND ALL / NOLOOP PATH (flag find_path_all) return every walk of 1 .. UPTO edges from a source to a target, NOLOOP
+// those without a repeated vertex, so the answer is a layered edge set and not walks:
+//   to side  seed / expand / settle from the targets, to depth UPTO - 1; after depth d the seen words are copied to
+//            cum[d]: the targets within d edges of each row
+//   walk     one launch per layer i of the from side (k_path_walk), layer 0 being the source rows: an edge into row r
+//            with m = cum[UPTO - 1 - i][r] != 0 is the i-th step of a walk that can still arrive, and is emitted with
+//            (i, m); r joins layer i + 1 once (a per-row stamp raised by atomicMax), whatever layers it was in before
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,11 +72,11 @@ __global__ __launch_bounds__(256) void k_path_seed(const uint32_t* rowsIn, uint6
         const uint64_t m = perEntry ? 1ULL << (i & 63) : 1ULL;
         const uint64_t idx = waveAppend(keep, count);
         if (keep) {                                               // distinct vids: distinct rows, one writer each
-            seen[g] = m;
+            if (seen) seen[g] = m;
             if (newD) newD[g] = m;
-            lvl[g] = 0;
+            if (lvl) lvl[g] = 0;
             outRows[idx] = g;
-            outMask[idx] = m;
+            if (outMask) outMask[idx] = m;
         }
     }
 }
@@ -207,7 +215,7 @@ __global__ __launch_bounds__(256) void k_path_sweep(PathSweepArgs a) {
                 pe.rank = pathRank(a.hs, s, p);
                 pe.mask = m;
                 pe.type = a.reverse ? -a.hs.etype[s] : a.hs.etype[s];
-                pe.pad = 0;
+                pe.layer = 0;
                 buf[atomicAdd(&cnt, 1u)] = pe;                    // cnt <= kPathBuf - 256 before the adds
             }
             __syncthreads();
@@ -230,6 +238,85 @@ __global__ __launch_bounds__(256) void k_path_sweep(PathSweepArgs a) {
     if (have) flush(have);
 }
 
+// FIND ALL / NOLOOP PATH, one layer of the from side: k_path_sweep's loop, LDS buffer and flush with another
+// test per edge. Nothing a lane reads here is written by this launch but stamp[], and that only through its atomicMax.
+__global__ __launch_bounds__(256) void k_path_walk(PathWalkArgs a) {
+    __shared__ PathEdge buf[kPathBuf];
+    __shared__ uint32_t cnt;
+    __shared__ uint64_t base;
+    __shared__ uint32_t trips[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long* fill = reinterpret_cast<unsigned long long*>(&a.S->edges);
+    unsigned long long* listed = reinterpret_cast<unsigned long long*>(&a.S->touched[0]);
+    const uint32_t mark = static_cast<uint32_t>(a.layer) + 2;     // stamp[r] = 2 + the last layer that listed r; 0: none
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    auto flush = [&](uint32_t have) {                             // called by the whole workgroup, after a barrier
+        if (threadIdx.x == 0) base = atomicAdd(fill, static_cast<unsigned long long>(have));
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < have; j += 256) {
+            const uint64_t o = base + j;
+            if (o < a.cap) a.out[o] = buf[j];                     // past the capacity only the count goes on: the host refuses
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) cnt = 0;
+        __syncthreads();
+    };
+    const uint64_t nEnt = a.n * static_cast<uint64_t>(a.hs.n);
+    for (uint64_t e0 = static_cast<uint64_t>(blockIdx.x) * 4; e0 < nEnt; e0 += static_cast<uint64_t>(gridDim.x) * 4) {   // uniform in the workgroup
+        const uint64_t w = e0 + wave;
+        uint32_t row = 0;
+        int s = 0;
+        uint64_t b = 0, e = 0;
+        if (w < nEnt) {
+            s = static_cast<int>(w % a.hs.n);
+            row = a.rows[w / a.hs.n];
+            b = a.hs.off[s][row];
+            e = a.hs.off[s][row + 1];
+        }
+        if (lane == 0) trips[wave] = static_cast<uint32_t>((e - b + 63) / 64);
+        __syncthreads();
+        const uint32_t T = max(max(trips[0], trips[1]), max(trips[2], trips[3]));
+        for (uint32_t it = 0; it < T; it++) {                     // uniform in the workgroup: the barriers below
+            const uint64_t p = b + static_cast<uint64_t>(it) * 64 + lane;
+            uint64_t m = 0;
+            uint32_t g = kNoRow;
+            if (p < e) {
+                g = a.hs.dgid[s][p];
+                if (g != kNoRow) m = a.cum[g];
+            }
+            bool list = false;
+            if (m) {
+                PathEdge pe;
+                pe.src = a.vid[row];
+                pe.dst = a.vid[g];
+                pe.rank = pathRank(a.hs, s, p);
+                pe.mask = m;
+                pe.type = a.hs.etype[s];
+                pe.layer = a.layer;
+                buf[atomicAdd(&cnt, 1u)] = pe;                    // cnt <= kPathBuf - 256 before the adds
+                if (a.next) list = atomicMax(a.stamp + g, mark) < mark;   // a row may be in many layers, once in each
+            }
+            const uint64_t idx = waveAppend(list, listed);        // every lane of the wave is here: T is uniform
+            if (list) {
+                if (idx < a.nextCap) a.next[idx] = g;
+                else a.S->err = 1;
+            }
+            __syncthreads();
+            const uint32_t have = cnt;
+            __syncthreads();                                      // everyone has read cnt before the next adds
+            if (have > kPathBuf - 256) {
+                flush(have);
+                if (threadIdx.x == 0) atomicAdd(&a.S->loopFlushes, 1u);
+            }
+        }
+        __syncthreads();                                          // trips[] is read before the next round writes it
+    }
+    __syncthreads();
+    const uint32_t have = cnt;
+    if (have) flush(have);
+}
+
 __global__ __launch_bounds__(256) void k_path_clear(const uint32_t* rows, uint64_t n, uint64_t* arr) {
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * 256) arr[rows[i]] = 0;
 }
@@ -242,7 +329,7 @@ unsigned pathGrid(uint64_t items, uint64_t perBlock, uint32_t gridMax = 0) {
 
 int launchPathSeed(const uint32_t* rowsIn, uint64_t n, int perEntry, uint64_t* seen, uint64_t* newD, uint8_t* lvl, uint32_t* outRows,
                    uint64_t* outMask, uint64_t* count, hipStream_t s) {
-    if (!rowsIn || !seen || !lvl || !outRows || !outMask || !count || (perEntry && n > 64)) return 1;
+    if (!rowsIn || !outRows || !count || (perEntry && n > 64)) return 1;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_path_seed, dim3(pathGrid(n, 256)), dim3(256), 0, s, rowsIn, n, perEntry, seen, newD, lvl, outRows, outMask,
                        reinterpret_cast<unsigned long long*>(count));
@@ -283,6 +370,13 @@ int launchPathSweep(const PathSweepArgs& a, bool meet, hipStream_t s) {
     const dim3 grid(pathGrid(a.n * a.hs.n, 4, a.gridMax));
     if (meet) hipLaunchKernelGGL(k_path_sweep<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_path_sweep<false>, grid, dim3(256), 0, s, a);
+    return static_cast<int>(hipGetLastError());
+}
+
+int launchPathWalk(const PathWalkArgs& a, hipStream_t s) {
+    if (!a.rows || !a.vid || !a.cum || !a.stamp || !a.out || !a.S || a.layer < 0) return 1;
+    if (a.n == 0 || a.hs.n == 0) return 0;
+    hipLaunchKernelGGL(k_path_walk, dim3(pathGrid(a.n * a.hs.n, 4, a.gridMax)), dim3(256), 0, s, a);
     return static_cast<int>(hipGetLastError());
 }
 

@@ -607,11 +607,12 @@ int launchSetProbe(const SetArgs& a, int side, hipStream_t s);
 // atomicOr only.
 constexpr uint32_t kPathBuf = 1024;                 // path-DAG edges a workgroup collects in LDS before it reserves output space
 constexpr uint32_t kPathGridMax = 2048;
+constexpr uint32_t kPathAllUpto = 8;                // FIND ALL / NOLOOP PATH: the most UPTO (cum[] is UPTO words a row)
 struct PathEdge {                                   // one edge of the path DAG, in path orientation (src nearer the sources)
     int64_t src, dst, rank;
     uint64_t mask;                                  // the targets whose shortest paths use it
     int32_t type;                                   // signed, as the path prints it
-    int32_t pad;
+    int32_t layer;                                  // ALL / NOLOOP: the step of a walk the edge is (from 0); SHORTEST: 0
 };
 struct PathState {
     uint64_t touched[2];                            // rows an expansion reached first, per side
@@ -621,7 +622,8 @@ struct PathState {
     uint32_t loopFlushes;                           // LDS buffer flushes inside a sweep's edge loop
     uint32_t err;                                   // a list past its capacity: cannot be
 };
-// level 0 of a side: every looked-up row (kNoRow: the vid has no vertex) gets bit `firstBit + (perEntry ? i : 0)`
+// level 0 of a side: every looked-up row (kNoRow: the vid has no vertex) gets bit `firstBit + (perEntry ? i : 0)`;
+// seen, newD, lvl and outMask may be null (the from side of ALL / NOLOOP needs the list of rows only)
 int launchPathSeed(const uint32_t* rowsIn, uint64_t n, int perEntry, uint64_t* seen, uint64_t* newD, uint8_t* lvl,
                    uint32_t* outRows, uint64_t* outMask, uint64_t* count, hipStream_t s);
 // every edge of a level's rows ORs the row's bits into inc[dst]; the lane whose OR found inc[dst] == 0 lists dst
@@ -659,6 +661,26 @@ struct PathSweepArgs {
 // whose bits are not found yet; the bits join keepNext[row], keepT[dst] and S->found[0]
 int launchPathSweep(const PathSweepArgs& a, bool meet, hipStream_t s);
 int launchPathClear(const uint32_t* rows, uint64_t n, uint64_t* arr, hipStream_t s);
+// FIND ALL / NOLOOP PATH: one layer of the from side's walk. An edge of a layer row into row r is the layer-th step of
+// a walk that can still end at a target iff m = cum[r] != 0, cum being the to side's "targets within UPTO - 1 - layer
+// edges" word per row: it is emitted with m, and r is listed in `next` (null on the last layer) once, by the lane
+// whose atomicMax raised stamp[r] to layer + 2. S->touched[0] counts the listed rows.
+struct PathWalkArgs {
+    const uint32_t* rows;                           // the layer's rows, a wave per (row, slot)
+    uint64_t n;
+    HopSlots hs;
+    const int64_t* vid;
+    const uint64_t* cum;
+    uint32_t* stamp;
+    uint32_t* next;
+    uint64_t nextCap;
+    PathEdge* out;
+    uint64_t cap;
+    PathState* S;
+    int32_t layer;
+    uint32_t gridMax;
+};
+int launchPathWalk(const PathWalkArgs& a, hipStream_t s);
 
 // FETCH PROP ON tags / an edge type over keys in HBM (fetch.hip; ngx_fetch). Keys are read in place at their stored
 // widths, sign-extended (GroupCol, as the set operator reads a result's columns). Three steps, every one a sweep of

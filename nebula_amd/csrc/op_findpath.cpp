@@ -1,4 +1,5 @@
-// FIND SHORTEST PATH (ngx_find_path): the host driver of findpath.hip.
+// FIND SHORTEST | ALL | NOLOOP PATH (ngx_find_path): the host driver of findpath.hip.
+#include <unordered_map>
 #include <unordered_set>
 
 #include "engine_ctx.h"
@@ -13,6 +14,7 @@ struct PathResultHolder {
     std::vector<int32_t> types, etype;
     std::vector<int64_t> src, dst, rank;
     std::vector<uint64_t> mask;
+    std::vector<uint8_t> layer;
 };
 
 // one side's levels: device lists of (row, bits) and their sizes
@@ -22,11 +24,170 @@ struct PathLevels {
     std::vector<uint64_t> n;
 };
 
+// the rows of the sentence's vids, the sources first (kNoRow: a vid without a vertex, which takes no part)
+const uint32_t* pathSeedRows(ngx_ctx* c, const Space& sp, const DeviceGraph& d, const ngx_path_plan& p) {
+    std::vector<int32_t> parts;
+    std::vector<int64_t> vids(p.from, p.from + p.nfrom);
+    vids.insert(vids.end(), p.to, p.to + p.nto);
+    for (int64_t v : vids) parts.push_back(idHash(v, sp.numParts));
+    const uint64_t n = vids.size();
+    int64_t* dv = c->seedVid.get<int64_t>(n * 2);                 // vids, then parts
+    int32_t* dpart = reinterpret_cast<int32_t*>(dv + n);
+    stageSeeds(c, parts, vids, dpart, dv);
+    uint32_t* rowsIn = c->fpSeed.get<uint32_t>(n);
+    if (launchIndexLookup(dpart, dv, n, d.vindex, rowsIn, c->stream)) throw Error{NGX_E_DEVICE, "lookup"};
+    return rowsIn;
+}
+
+void pathLevelBufs(ngx_ctx* c, int side, size_t level, uint64_t n, uint32_t*& rows, uint64_t*& masks) {
+    if (c->fpRows[side].size() <= level) { c->fpRows[side].resize(level + 1); c->fpMasks[side].resize(level + 1); }
+    rows = c->fpRows[side][level].get<uint32_t>(std::max<uint64_t>(n, 1));
+    masks = c->fpMasks[side][level].get<uint64_t>(std::max<uint64_t>(n, 1));
+}
+
+// the device's edges into the result's arrays
+void pathEdgesOut(PathResultHolder& R, const std::vector<PathEdge>& host) {
+    const uint64_t m = host.size();
+    R.src.resize(m); R.dst.resize(m); R.rank.resize(m); R.etype.resize(m); R.mask.resize(m);
+    for (uint64_t i = 0; i < m; i++) {
+        R.src[i] = host[i].src; R.dst[i] = host[i].dst; R.rank[i] = host[i].rank; R.etype[i] = host[i].type; R.mask[i] = host[i].mask;
+    }
+    R.r.nedges = m;
+    R.r.src = R.src.data(); R.r.dst = R.dst.data(); R.r.rank = R.rank.data(); R.r.type = R.etype.data(); R.r.mask = R.mask.data();
+}
+
+// FIND ALL / NOLOOP PATH (flag find_path_all): the to side's cumulative target sets per depth, then the
+// from side layer by layer. hs[0]: the sentence's types, hs[1]: the opposite ones.
+int32_t findAllPaths(ngx_ctx* c, const ngx_path_plan& p, const Space& sp, const DeviceGraph& d, const HopSlots (&hs)[2], PathResultHolder& R) {
+    const uint64_t nS = p.nfrom, nT = p.nto, upto = p.upto;
+    resultEvents(c);
+    const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
+    HIP_OK(hipEventRecord(ev0, c->stream));
+    const uint64_t G = std::max<uint64_t>(d.vglobal, 1);
+    uint64_t* inc = c->fpInc[1].get<uint64_t>(G);
+    uint64_t* seen = c->fpSeen[1].get<uint64_t>(G);
+    uint8_t* lvl = c->fpLvl[1].get<uint8_t>(G);                   // the settle writes it; nothing here reads it
+    uint32_t* touched = c->fpTouched[1].get<uint32_t>(G);
+    uint64_t* cum = c->fpCum.get<uint64_t>(upto * G);             // cum[d]: every depth reached is copied whole, none is read before
+    uint32_t* stamp = c->fpStamp.get<uint32_t>(G);
+    uint32_t* layerRows[2] = {c->fpTouched[0].get<uint32_t>(G), touched};   // the to side is done with its list when the layers start
+    HIP_OK(hipMemsetAsync(inc, 0, G * 8, c->stream));
+    HIP_OK(hipMemsetAsync(seen, 0, G * 8, c->stream));
+    HIP_OK(hipMemsetAsync(stamp, 0, G * 4, c->stream));
+    const uint64_t cap = static_cast<uint64_t>(c->pathRowsMax);
+    PathEdge* outDev = c->fpOut.get<PathEdge>(cap);
+    PathState* S = c->fpState.get<PathState>(1);
+    HIP_OK(hipMemsetAsync(S, 0, sizeof(PathState), c->stream));
+    PathState st{};
+    auto readState = [&] {
+        HIP_OK(hipMemcpyAsync(&st, S, sizeof st, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (st.err) throw Error{NGX_E_DEVICE, "find path: inconsistent counts"};
+    };
+
+    // ---- depth 0 and layer 0: the vids' rows
+    const uint32_t* rowsIn = pathSeedRows(c, sp, d, p);
+    uint32_t *rowsF, *rowsT;
+    uint64_t *masksF, *masksT;
+    pathLevelBufs(c, 0, 0, nS, rowsF, masksF);
+    pathLevelBufs(c, 1, 0, nT, rowsT, masksT);
+    if (launchPathSeed(rowsIn, nS, 0, nullptr, nullptr, nullptr, rowsF, nullptr, &S->nLevel[0], c->stream) ||
+        launchPathSeed(rowsIn + nS, nT, 1, seen, nullptr, lvl, rowsT, masksT, &S->nLevel[1], c->stream))
+        throw Error{NGX_E_DEVICE, "path seed"};
+    HIP_OK(hipMemcpyAsync(cum, seen, G * 8, hipMemcpyDeviceToDevice, c->stream));
+    readState();
+    uint64_t nLayer = st.nLevel[0], nLevel = st.nLevel[1];
+
+    // ---- the to side: cum[d] = the targets within d edges of each row, d = 0 .. UPTO - 1, until a level is empty
+    int32_t depths = 0;
+    uint64_t last = 0;                                            // the last depth copied: a deeper one reads as this one
+    for (uint64_t dep = 1; dep < upto && nLevel; dep++) {
+        HIP_OK(hipMemsetAsync(S, 0, offsetof(PathState, edges), c->stream));
+        c->timed("path_expand", 0, [&] {
+            if (launchPathExpand(rowsT, masksT, nLevel, hs[1], inc, touched, G, S, 1, c->stream)) throw Error{NGX_E_DEVICE, "path expand"};
+        });
+        depths++;
+        readState();                                              // the rows reached: they size the new level's lists
+        const uint64_t nTouched = st.touched[1];
+        pathLevelBufs(c, 1, dep, nTouched, rowsT, masksT);
+        c->timed("path_settle", 0, [&] {
+            if (launchPathSettle(touched, nTouched, inc, seen, nullptr, lvl, static_cast<uint8_t>(dep), rowsT, masksT, S, 1, c->stream))
+                throw Error{NGX_E_DEVICE, "path settle"};
+            HIP_OK(hipMemcpyAsync(cum + dep * G, seen, G * 8, hipMemcpyDeviceToDevice, c->stream));
+        });
+        last = dep;
+        readState();
+        nLevel = st.nLevel[1];
+    }
+
+    // ---- the from side: layer i's edges into rows that a target is within UPTO - 1 - i edges of
+    int32_t layers = 0;
+    bool tooMany = false;
+    const uint32_t* cur = rowsF;
+    for (uint64_t i = 0; i < upto && nLayer; i++) {
+        HIP_OK(hipMemsetAsync(S, 0, offsetof(PathState, edges), c->stream));
+        PathWalkArgs a{};
+        a.rows = cur;
+        a.n = nLayer;
+        a.hs = hs[0];
+        a.vid = d.vid;
+        a.cum = cum + std::min(upto - 1 - i, last) * G;
+        a.stamp = stamp;
+        a.next = i + 1 < upto ? layerRows[i & 1] : nullptr;
+        a.nextCap = G;
+        a.out = outDev;
+        a.cap = cap;
+        a.S = S;
+        a.layer = static_cast<int32_t>(i);
+        a.gridMax = c->pathGridMax;
+        c->timed("path_walk", 0, [&] { if (launchPathWalk(a, c->stream)) throw Error{NGX_E_DEVICE, "path walk"}; });
+        layers++;
+        readState();                                              // the next layer's rows, the edges so far
+        if (st.edges > cap) { tooMany = true; break; }
+        cur = layerRows[i & 1];
+        nLayer = st.touched[0];
+    }
+    c->findPathLoopFlushes += st.loopFlushes;
+    if (tooMany) {
+        c->collectTimings();
+        return fail(c, NGX_E_UNSUPPORTED, "find path: path edges above path_rows_max");
+    }
+    HIP_OK(hipEventRecord(ev1, c->stream));
+    std::vector<PathEdge> host(st.edges);
+    if (!host.empty()) HIP_OK(hipMemcpyAsync(host.data(), outDev, host.size() * sizeof(PathEdge), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
+    c->collectTimings();
+    pathEdgesOut(R, host);
+    std::unordered_map<int64_t, uint64_t> bitOf;
+    for (uint64_t j = 0; j < nT; j++) bitOf[p.to[j]] = 1ULL << j;
+    R.layer.resize(host.size());
+    uint64_t found = 0;
+    for (size_t i = 0; i < host.size(); i++) {
+        R.layer[i] = static_cast<uint8_t>(host[i].layer);
+        auto it = bitOf.find(host[i].dst);
+        if (it != bitOf.end()) found |= it->second;
+    }
+    R.r.layer = R.layer.data();
+    R.r.found = found;
+    R.r.levels = depths + layers;
+    R.r.device_ms = ms;
+    c->findPathDevice++;
+    c->findPathLevels += static_cast<uint64_t>(depths + layers);
+    c->findPathLayers += static_cast<uint64_t>(layers);
+    c->findPathEdges += host.size();
+    return NGX_OK;
+}
+
 int32_t findPath(ngx_ctx* c, const ngx_path_plan& p, PathResultHolder& R) {
-    if (p.kind != NGX_PATH_SHORTEST) return fail(c, NGX_E_UNSUPPORTED, "find path: ALL and NOLOOP enumerate walks, not levels");
+    const bool layered = p.kind == NGX_PATH_ALL || p.kind == NGX_PATH_NOLOOP;
+    if (p.kind != NGX_PATH_SHORTEST && !(layered && c->findPathAll))
+        return fail(c, NGX_E_UNSUPPORTED, "find path: ALL and NOLOOP enumerate walks, not levels");
     if (p.direction != NGX_DIR_FORWARD && p.direction != NGX_DIR_REVERSELY) return fail(c, NGX_E_UNSUPPORTED, "find path: BIDIRECT");
     if (c->world > 1) return fail(c, NGX_E_UNSUPPORTED, "find path: world > 1 needs the levels exchanged");
     if (p.upto < 1 || p.upto > 500) return fail(c, NGX_E_UNSUPPORTED, "find path: UPTO outside 1 .. 500");
+    if (layered && p.upto > kPathAllUpto) return fail(c, NGX_E_UNSUPPORTED, "find path: UPTO above 8 for ALL and NOLOOP");
     Space* spp = findSpace(c, p.space);
     if (!spp || !spp->dev) return fail(c, NGX_E_NOT_LOADED, "space not committed");
     const Space& sp = *spp;
@@ -79,6 +240,7 @@ int32_t findPath(ngx_ctx* c, const ngx_path_plan& p, PathResultHolder& R) {
         for (int s = 0; s < hs[side].n; s++)
             if (hs[side].eflags[s]) return fail(c, NGX_E_UNSUPPORTED, "find path: edges with empty or unreadable values");
     }
+    if (layered) return findAllPaths(c, p, sp, d, hs, R);
 
     resultEvents(c);
     const hipEvent_t ev0 = c->gbEv[0], ev1 = c->gbEv[1];
@@ -108,22 +270,9 @@ int32_t findPath(ngx_ctx* c, const ngx_path_plan& p, PathResultHolder& R) {
 
     // ---- level 0: the vids' rows (a vid without a vertex has none and takes no part)
     PathLevels lv[2];
-    auto levelBufs = [&](int side, size_t level, uint64_t n, uint32_t*& rows, uint64_t*& masks) {
-        if (c->fpRows[side].size() <= level) { c->fpRows[side].resize(level + 1); c->fpMasks[side].resize(level + 1); }
-        rows = c->fpRows[side][level].get<uint32_t>(std::max<uint64_t>(n, 1));
-        masks = c->fpMasks[side][level].get<uint64_t>(std::max<uint64_t>(n, 1));
-    };
+    auto levelBufs = [&](int side, size_t level, uint64_t n, uint32_t*& rows, uint64_t*& masks) { pathLevelBufs(c, side, level, n, rows, masks); };
     {
-        std::vector<int32_t> parts;
-        std::vector<int64_t> vids(p.from, p.from + nS);
-        vids.insert(vids.end(), p.to, p.to + nT);
-        for (int64_t v : vids) parts.push_back(idHash(v, sp.numParts));
-        const uint64_t n = vids.size();
-        int64_t* dv = c->seedVid.get<int64_t>(n * 2);             // vids, then parts
-        int32_t* dpart = reinterpret_cast<int32_t*>(dv + n);
-        stageSeeds(c, parts, vids, dpart, dv);
-        uint32_t* rowsIn = c->fpSeed.get<uint32_t>(n);
-        if (launchIndexLookup(dpart, dv, n, d.vindex, rowsIn, c->stream)) throw Error{NGX_E_DEVICE, "lookup"};
+        const uint32_t* rowsIn = pathSeedRows(c, sp, d, p);
         for (int side = 0; side < 2; side++) {
             uint32_t* rows;
             uint64_t* masks;
@@ -259,12 +408,7 @@ int32_t findPath(ngx_ctx* c, const ngx_path_plan& p, PathResultHolder& R) {
     float ms = 0;
     HIP_OK(hipEventElapsedTime(&ms, ev0, ev1));
     c->collectTimings();
-    R.src.resize(m); R.dst.resize(m); R.rank.resize(m); R.etype.resize(m); R.mask.resize(m);
-    for (uint64_t i = 0; i < m; i++) {
-        R.src[i] = host[i].src; R.dst[i] = host[i].dst; R.rank[i] = host[i].rank; R.etype[i] = host[i].type; R.mask[i] = host[i].mask;
-    }
-    R.r.nedges = m;
-    R.r.src = R.src.data(); R.r.dst = R.dst.data(); R.r.rank = R.rank.data(); R.r.type = R.etype.data(); R.r.mask = R.mask.data();
+    pathEdgesOut(R, host);
     R.r.found = found;
     R.r.levels = levels;
     R.r.device_ms = ms;

@@ -229,7 +229,7 @@ class PathPlanC(ctypes.Structure):
 class PathResultC(ctypes.Structure):
     _fields_ = [("code", c_i32), ("nedge_names", c_i32), ("edge_names", P(ctypes.c_char_p)), ("edge_types", P(c_i32)),
                 ("nedges", c_u64), ("src", P(c_i64)), ("dst", P(c_i64)), ("type", P(c_i32)), ("rank", P(c_i64)),
-                ("mask", P(c_u64)), ("found", c_u64), ("levels", c_i32), ("device_ms", c_dbl)]
+                ("mask", P(c_u64)), ("found", c_u64), ("levels", c_i32), ("device_ms", c_dbl), ("layer", P(ctypes.c_uint8))]
 
 
 FETCH_VERTEX, FETCH_EDGE = 0, 1                                 # NGX_FETCH_*
@@ -526,6 +526,7 @@ class Engine:
     device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
     device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
     device_find_path = True                    # find_path(space, sentence) searches FIND SHORTEST PATH in HBM
+    path_paths_max = 1 << 20                   # find_path: FIND ALL / NOLOOP PATH answers with more walks are refused ("find path: more than ... paths")
     device_fetch = True                        # fetch(space, spec) / go_fetch(space, go, spec) look keys up and gather in HBM
     device_lookup = True                       # lookup(space, spec) scans a tag's / an edge type's columns in HBM
 
@@ -1019,7 +1020,10 @@ class Engine:
         edges, hop_frontier [levels expanded], path_found the found targets' bits, device_ms the call's.
         NGX_E_UNSUPPORTED with a text starting "find path:" comes back as a result with that code (the caller runs the host restatement); any other failure
         as a result with its code and text too. rows=False skips the enumeration (GoResult.dev_cols keeps the edge
-        arrays src, dst, type, rank, mask)."""
+        arrays src, dst, type, rank, mask).
+        With flag find_path_all set, FIND ALL PATH and FIND NOLOOP PATH are answered too: the device returns the layered
+        edge set (dev_cols gains a sixth array, each edge's layer), findpath.paths_from_layers enumerates the walks, and
+        a sentence with more than path_paths_max ALL walks is refused like any other (counted here, after the call)."""
         from . import findpath
         if isinstance(s, str):
             s = ngql.parse_find_path(s)
@@ -1049,9 +1053,21 @@ class Engine:
             cols = (_arr(o.src, m, np.int64), _arr(o.dst, m, np.int64), _arr(o.type, m, np.int32), _arr(o.rank, m, np.int64),
                     _arr(o.mask, m, np.uint64))
             res.dev_cols = list(cols)
+            layered = s.kind != "SHORTEST"
+            if layered:
+                res.dev_cols.append(_arr(o.layer, m, np.uint8))
             if rows:
                 type_names = {o.edge_types[i]: o.edge_names[i].decode() for i in range(o.nedge_names)}
-                res.rows = [(("path", t),) for t in findpath.paths_from_dag(fv, tv, *cols, type_names)]
+                if layered:
+                    try:
+                        texts = findpath.paths_from_layers(fv, tv, res.dev_cols[5], *cols, type_names, s.kind == "NOLOOP",
+                                                           self.path_paths_max)
+                    except findpath.FindPathRefusal as e:         # the walks are counted here: refused like the library's own
+                        return GoResult(ok=False, error=str(e), code=E_UNSUPPORTED, col_types=[], rows=[], device_ms=o.device_ms,
+                                        go_nrows=o.nedges, hop_frontier=[o.levels], path_found=int(o.found))
+                else:
+                    texts = findpath.paths_from_dag(fv, tv, *cols, type_names)
+                res.rows = [(("path", t),) for t in texts]
                 res.nrows = len(res.rows)
                 res.col_types = [findpath.T_PATH] if res.rows else []
             return res

@@ -26,7 +26,8 @@ A path is a cell ("path", text) with the reference's test rendering (TraverseTes
 FindPathExecutor hands no result on: it never calls onResult_ and finishes with doFinish(kNext), so the sentence
 piped behind FIND PATH runs with inputs_ == nullptr. pipeline.py does the same: the next sentence gets no input.
 These functions serve every backend and are the specification of the device path (ngx_find_path,
-include/nebula_gn.h); paths_from_dag turns that call's path-DAG edges into the same rows.
+include/nebula_gn.h); paths_from_dag turns that call's path-DAG edges into the same rows for SHORTEST, and
+paths_from_layers its layered edges for ALL and NOLOOP.
 """
 from __future__ import annotations
 
@@ -41,6 +42,10 @@ T_PATH = 41                                                       # nebula::cpp2
 
 class FindPathError(Exception):
     """A failed Status of the executor; str() is the outcome's error text."""
+
+
+class FindPathRefusal(FindPathError):
+    """The device answer is not turned into rows here (text `find path: ...`): the caller runs the restatement."""
 
 
 # ----------------------------------------------------------------------------- FROM / TO
@@ -313,4 +318,54 @@ def paths_from_dag(sources: Sequence[int], targets: Sequence[int], src, dst, typ
                 continue
             for d, t, r in adj.get(v, ()):
                 stack.append((d, "%s<%s%s,%d>%d" % (text, "" if t >= 0 else "-", type_names[abs(t)], r, d)))
+    return rows
+
+
+def count_walks(sources: Sequence[int], targets: Sequence[int], layer, src, dst) -> int:
+    """The ALL walks of a layered edge set (paths_from_layers), without enumerating them: per layer the number of
+    walks that end at each vertex, summed over the targets."""
+    goal = set(int(v) for v in targets)
+    by_layer: Dict[int, List[Tuple[int, int]]] = {}
+    for i in range(len(src)):
+        by_layer.setdefault(int(layer[i]), []).append((int(src[i]), int(dst[i])))
+    ends = {int(v): 1 for v in sources}
+    total = 0
+    for k in range(max(by_layer) + 1 if by_layer else 0):
+        nxt: Dict[int, int] = {}
+        for u, v in by_layer.get(k, ()):
+            n = ends.get(u)
+            if n:
+                nxt[v] = nxt.get(v, 0) + n
+        total += sum(n for v, n in nxt.items() if v in goal)
+        ends = nxt
+    return total
+
+
+def paths_from_layers(sources: Sequence[int], targets: Sequence[int], layer, src, dst, typ, rank, mask,
+                      type_names: Dict[int, str], no_loop: bool, max_paths: int) -> List[str]:
+    """The paths of ngx_find_path's answer to ALL and NOLOOP: edge i is the layer[i]-th step (from 0) of some walk
+    from a source to a target of mask[i], from src[i] to dst[i] with the signed type typ[i] and rank[i]. A walk
+    starts at a source in layer 0 and follows only edges of its current layer; each time it stands on a target
+    after at least one edge it is a row. Every edge of the set leads on to a target within the layers left, so no
+    branch is followed in vain. NOLOOP drops a branch when it comes back to a vertex of its walk. The ALL walks are
+    counted first; above max_paths FindPathRefusal is raised and nothing is enumerated."""
+    n = count_walks(sources, targets, layer, src, dst)
+    if n > max_paths:
+        raise FindPathRefusal("find path: more than %d paths" % max_paths)
+    goal = set(int(v) for v in targets)
+    adj: Dict[Tuple[int, int], List[Tuple[int, int, int]]] = {}
+    for i in range(len(src)):
+        adj.setdefault((int(layer[i]), int(src[i])), []).append((int(dst[i]), int(typ[i]), int(rank[i])))
+    rows = []
+    for s in sources:
+        stack = [(int(s), 0, str(int(s)), (int(s),))]
+        while stack:
+            v, k, text, on = stack.pop()
+            if k and v in goal:
+                rows.append(text)
+            for d, t, r in adj.get((k, v), ()):
+                if no_loop and d in on:
+                    continue
+                stack.append((d, k + 1, "%s<%s%s,%d>%d" % (text, "" if t >= 0 else "-", type_names[abs(t)], r, d),
+                              on + (d,) if no_loop else on))
     return rows

@@ -10,7 +10,12 @@ configs[1]: RMAT scale 22, edge factor 16), run two ways on the same Engine:
 The host leg extends every walk by every neighbour, as graphd does; on a C2-sized graph that does not end in
 reasonable time, so it runs on a second, smaller graph when --host-scale is below --scale (0: not at all), and the
 device leg is measured there too so the two walls compare on one graph. Where both legs run their sorted rows are
-compared before anything is printed. One JSON line on stdout, and --out FILE writes it there too."""
+compared before anything is printed. One JSON line on stdout, and --out FILE writes it there too.
+
+--kind ALL | NOLOOP measures `FIND ALL PATH` / `FIND NOLOOP PATH` instead (flag find_path_all is set; --upto, at most
+8 for them). A sentence the device call refuses (path_rows_max, Engine.path_paths_max) is not an error then: the
+target count's entry reports how many sentences were refused and the last refusal's text, and the figures are over
+the sentences that were answered."""
 import argparse
 import json
 import os
@@ -45,7 +50,7 @@ def load(eng, space, scale, ef, parts, threads):
     log(f"RMAT scale {scale} loaded into space {space} in {time.time() - t0:.1f}s")
 
 
-def sentences(scale, ef, nt, n, threads):
+def sentences(scale, ef, nt, n, threads, kind="SHORTEST", upto=5):
     """n seeded sentences: a source of the bench's seed generator, nt other vids as targets."""
     from nebula_amd import datagen
     out = []
@@ -57,7 +62,7 @@ def sentences(scale, ef, nt, n, threads):
             v = rng.randrange(1 << scale)
             if v != seeds[0]:
                 to.add(v)
-        out.append("FIND SHORTEST PATH FROM %d TO %s OVER e UPTO 5 STEPS" % (seeds[0], ", ".join(map(str, sorted(to)))))
+        out.append("FIND %s PATH FROM %d TO %s OVER e UPTO %d STEPS" % (kind, seeds[0], ", ".join(map(str, sorted(to))), upto))
     return out
 
 
@@ -67,7 +72,8 @@ def measure(eng, space, scale, args, host):
     n = warmup + steps
     res = {}
     for nt in TARGETS:
-        qs = sentences(scale, args.ef, nt, n, args.threads)
+        qs = sentences(scale, args.ef, nt, n, args.threads, args.kind, args.upto)
+        refused, refusal = 0, ""
         dev_ms, dev_wall, host_wall, rows, edges, levels = [], [], [], 0, 0, 0
         kernel_ms = {}
         calls0 = eng.get_flag("find_path_device")
@@ -85,7 +91,10 @@ def measure(eng, space, scale, args, host):
             r = eng.find_path(space, q)
             dw = (time.perf_counter() - t) * 1e3
             if not r.ok:
-                raise RuntimeError(r.error)
+                if args.kind == "SHORTEST" or not r.error.startswith("find path:"):
+                    raise RuntimeError(r.error)
+                refused, refusal = refused + 1, r.error
+                continue
             if host:
                 t = time.perf_counter()
                 h = pipeline.run(eng, space, q, ["e"], find_path=True, device_find_path=False)
@@ -103,11 +112,14 @@ def measure(eng, space, scale, args, host):
             rows += r.nrows
             edges += r.go_nrows
             levels += r.hop_frontier[0]
-        one = {"steps": steps, "warmup": warmup, "device_ms": mean(dev_ms), "device_ms_min": round(min(dev_ms), 3), "device_wall_ms": mean(dev_wall),
-               "host_wall_ms": mean(host_wall), "paths_per_step": round(rows / steps, 1),
-               "dag_edges_per_step": round(edges / steps, 1), "levels_per_step": round(levels / steps, 1),
-               "on_device": eng.get_flag("find_path_device") - calls0 >= n}
-        if host:
+        done = max(len(dev_ms), 1)
+        one = {"steps": steps, "warmup": warmup, "device_ms": mean(dev_ms), "device_ms_min": round(min(dev_ms), 3) if dev_ms else None,
+               "device_wall_ms": mean(dev_wall), "host_wall_ms": mean(host_wall), "paths_per_step": round(rows / done, 1),
+               "dag_edges_per_step": round(edges / done, 1), "levels_per_step": round(levels / done, 1),
+               "on_device": eng.get_flag("find_path_device") - calls0 >= n - refused}
+        if refused:
+            one["refused"], one["refusal"] = refused, refusal
+        if host and host_wall:
             one["wall_ratio"] = round(mean(host_wall) / mean(dev_wall), 2)
         if args.kernels:
             one["kernel_ms_per_call"] = {k: round(v / steps, 3) for k, v in kernel_ms.items() if v > 0}
@@ -128,14 +140,18 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--threads", type=int, default=16)
     p.add_argument("--kernels", action="store_true", help="per-launch-group device times (profiling on, a run of its own)")
+    p.add_argument("--kind", default="SHORTEST", choices=["SHORTEST", "ALL", "NOLOOP"])
+    p.add_argument("--upto", type=int, default=5)
     p.add_argument("--out", default="")
     args = p.parse_args(argv)
 
     from nebula_amd import datagen, engine
 
     eng = engine.Engine(0)
+    if args.kind != "SHORTEST":
+        eng.set_flag("find_path_all", 1)
     out = {"scale": args.scale, "host_scale": args.host_scale, "ef": args.ef, "steps": args.steps, "warmup": args.warmup,
-           "counters_collected": False}
+           "kind": args.kind, "upto": args.upto, "counters_collected": False}
     load(eng, datagen.RMAT_SPACE, args.scale, args.ef, args.parts, args.threads)
     if args.host_scale == args.scale:
         out["device_and_host"] = measure(eng, datagen.RMAT_SPACE, args.scale, args, True)
