@@ -930,6 +930,12 @@ int32_t ngx_kernel_stats(ngx_ctx* ctx, const ngx_kernel_stat** out, int32_t* n);
  *          single-load YIELD columns) issues the edge-column loads of a dense final hop before it builds the
  *          frontier bits from the marks; 0: the generic body. Read-only "dense_early_finals" (launches that
  *          took it), "jit_dense_vgprs" / "jit_dense_scratch" (that kernel's registers and scratch). Same results.
+ *   "batch_pair_finals"  1 (default) / 0: in a pipelined ngx_go_batch at world 1, queries 2k and 2k + 1 whose dense,
+ *          loads-first final hops share the generated module, slot, literals, widths and reservation geometry
+ *          (they differ in their seeds only) run them as one launch that reads the slot's columns once and
+ *          writes both queries' rows; any other second query makes the first one's final hop run alone, as
+ *          with 0. Same results. Read-only "paired_finals" (launches that served two queries),
+ *          "jit_dense2_vgprs" / "jit_dense2_scratch" (that kernel's registers and scratch).
  *   "final_nt_loads" / "final_nt_stores"  0 (default) / 1: the generated GO final hop loads its columns /
  *          stores its rows non-temporally (not kept in L2). Same results.
  * Read-only counters for ngx_get_flag: "jit_compiled", "jit_hits", "jit_failed", "jit_compile_us",

@@ -124,6 +124,27 @@ struct GoJob {
     int32_t rc = NGX_OK;
     uint64_t nrows = 0, edges = 0, digest[3] = {0, 0, 0};
 };
+// Flag batch_pair_finals: the first query (2k) of a candidate pair does not launch its dense final hop; it
+// leaves here what the launch needs and defers as usual. The second (2k + 1) either launches one kernel for
+// both (final_kernels.h finalBodyDense2) with both closes behind it, or flushes the held launch as the
+// single launch it would have been (flushHeldFinal) and launches itself as usual. The slot holds everything
+// the flush needs, so the batch loop can flush from the main context. A held launch is always enqueued
+// before anyone waits for its row count: the loop flushes before it resumes the holder, and when the second
+// query hands control back with the slot still filled (it finished or failed before its final hop).
+struct HeldFinal {
+    bool valid = false;
+    int32_t idx = -1;                                  // the batch query that holds
+    FinalArgs a;
+    unsigned grid = 0;
+    std::shared_ptr<const JitKernels> kj;              // the module both queries must share
+    int lane = 0;
+    hipStream_t fs = nullptr;                          // its final stream: the waits of its FinalStreamScope are on it
+    hipStream_t closeStream = nullptr;                 // where its close would run (null: after the hop on fs)
+    hipEvent_t frontEv = nullptr;                      // its front stream at the hand-off
+    bool closePending = false;                         // its lane's last close was still pending then
+    // (its program image — code, column types, literal pool — stays where it is: LaneState::progLast of its
+    // parked lane, which nothing rewrites before the holder runs on)
+};
 struct GoPipe {
     enum { kRunning = 0, kDeferred = 1, kPreFinal = 2, kDone = 3 };
     ucontext_t main;
@@ -132,6 +153,9 @@ struct GoPipe {
     bool holdFinals = false;                           // digests: a final hop waits for the deferred query
     const ngx_go_plan* const* plans = nullptr;
     int32_t n = 0;
+    bool pairFinals = false;                           // flag batch_pair_finals at world 1
+    HeldFinal held;
+    int32_t heldFailed = -1;                           // the query whose held launch (or its close) failed to enqueue
 };
 
 namespace {
@@ -780,6 +804,87 @@ void streamAfter(hipStream_t to, hipStream_t from, hipEvent_t ev) {
     HIP_OK(hipStreamWaitEvent(to, ev, 0));
 }
 
+// batch_pair_finals: queries idx (even) and idx + 1 are a candidate pair, decided by the plans alone
+bool pairCandidate(const GoPipe* P, int32_t idx) {
+    return P && P->pairFinals && idx >= 0 && (idx & 1) == 0 && idx + 1 < P->n && pipelinable(*P->plans[idx]) &&
+           pipelinable(*P->plans[idx + 1]);
+}
+
+// the lane's close event recorded on `s` (the lane's next final hop waits for it)
+void recordLaneClose(ngx_ctx* c, int lane, hipStream_t s) {
+    hipEvent_t& ev = c->laneCloseEv[lane];
+    if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(ev, s));
+    c->laneClosePending[lane] = true;
+}
+
+// The held final hop as the single launch it would have been: the loads-first kernel on its own final stream
+// (behind the waits its FinalStreamScope enqueued there: its front stream, its lane's last close), then its
+// close and the lane's close event. Uses the slot alone (any lane may be active; the main context calls it).
+void flushHeldFinal(ngx_ctx* c) {
+    GoPipe* P = c->pipe;
+    if (!P || !P->held.valid) return;
+    HeldFinal& h = P->held;
+    h.valid = false;
+    try {
+        void* args[] = {&h.a};
+        HIP_OK(hipModuleLaunchKernel(h.kj->finalDense, h.grid, 1, 1, 256u, 1, 1, 0, h.fs, args, nullptr));
+        hipStream_t cs = h.fs;
+        if (h.closeStream) {
+            streamAfter(h.closeStream, h.fs, c->pipeEvent(4));
+            cs = h.closeStream;
+        }
+        if (launchFinalClose(h.a, cs)) throw Error{NGX_E_DEVICE, "final close"};
+        recordLaneClose(c, h.lane, cs);
+    } catch (const Error&) {
+        // the holder fails when it resumes (no wait for a count). Its kernel may have been enqueued before the
+        // failing call and may still write the lane's rows while the query returns: rows nobody reads, in
+        // arrays the lane keeps; the lane's next final hop is ordered behind the final streams by the failed
+        // query's drain (goCall synchronises them)
+        P->heldFailed = h.idx;
+    }
+    h.kj.reset();
+}
+
+// Whether the held query's final hop and this one's (`m`, module kj, `grid` workgroups, program image `prog`)
+// differ in nothing the shared half of finalBodyDense2 reads: only their frontiers and their own outputs.
+// heldProg / prog: the two queries' program images (the literal pool's bytes are in no FinalArgs field).
+// Every FinalArgs field the shared half reads is compared here: kargs.h FinalArgs points back to this list.
+bool pairable(const HeldFinal& h, const std::string& heldProg, const FinalArgs& m, const JitKernels* kj, unsigned grid,
+              const std::string& prog) {
+    const FinalArgs& a = h.a;
+    if (h.kj.get() != kj || kj == nullptr || kj->finalDense2 == nullptr || h.grid != grid || heldProg != prog) return false;
+    if (std::memcmp(a.kc, m.kc, sizeof(a.kc)) != 0 || std::memcmp(a.kl, m.kl, sizeof(a.kl)) != 0) return false;
+    const HopSlots &x = a.hs, &y = m.hs;
+    if (x.n != 1 || y.n != 1 || x.slotIdx[0] != y.slotIdx[0] || x.etype[0] != y.etype[0] || x.off[0] != y.off[0] ||
+        x.dgid[0] != y.dgid[0] || x.dst[0] != y.dst[0] || x.rank[0] != y.rank[0] || x.dstW[0] != y.dstW[0] ||
+        x.rankW[0] != y.rankW[0] || x.rankC[0] != y.rankC[0] || x.eflags[0] != y.eflags[0] || x.colBase[0] != y.colBase[0])
+        return false;
+    if (a.env.slots != m.env.slots || a.env.tags != m.env.tags || a.env.cols != m.env.cols || a.env.dtags != m.env.dtags ||
+        a.env.dcols != m.env.dcols || a.env.input != m.env.input || a.dstMap != m.dstMap)
+        return false;
+    if (a.E != m.E || a.nEnt != m.nEnt || a.estart != m.estart || a.chunkFirst != m.chunkFirst) return false;
+    if (a.propsMask != m.propsMask || a.ttlMask != m.ttlMask || a.wIsP != m.wIsP || a.mask != m.mask) return false;
+    if (a.ttlMask != 0 && (a.now != m.now || a.env.now != m.env.now || a.ttlCol[0] != m.ttlCol[0] || a.ttlDur[0] != m.ttlDur[0]))
+        return false;
+    // equal output widths and the same set of outputs
+    if (a.oSrcW != m.oSrcW || a.oDstW != m.oDstW || a.oRankW != m.oRankW || a.nY != m.nY) return false;
+    if ((a.oSrc == nullptr) != (m.oSrc == nullptr) || (a.oDst == nullptr) != (m.oDst == nullptr) ||
+        (a.oRank == nullptr) != (m.oRank == nullptr) || (a.oType == nullptr) != (m.oType == nullptr) ||
+        (a.oCols == nullptr) != (m.oCols == nullptr) || a.nY > kInlineCols)
+        return false;
+    for (int32_t k = 0; k < a.nY; k++) {
+        const OutCol &p = a.oColsIn[k], &q = m.oColsIn[k];
+        if (p.w != q.w || (p.x == nullptr) != (q.x == nullptr) || (p.len == nullptr) != (q.len == nullptr) ||
+            (p.t == nullptr) != (q.t == nullptr))
+            return false;
+    }
+    if (a.resvG != m.resvG || a.resvShift != m.resvShift || a.resvStride != m.resvStride) return false;
+    if ((a.dynTiles == nullptr) != (m.dynTiles == nullptr)) return false;
+    return a.denseMark != nullptr && m.denseMark != nullptr && a.fin == nullptr && m.fin == nullptr &&
+           a.strOut == nullptr && m.strOut == nullptr;
+}
+
 // A record hop during a pipelined batch: the deferrable last final hop runs on the final stream, after
 // this query's hops on the front stream, and its k_final_close on the close stream after it; any other
 // record hop stays on the front stream, after every final hop and close enqueued so far
@@ -795,6 +900,8 @@ struct FinalStreamScope {
             saved = c->stream;
             c->stream = fs;
         } else {
+            // (every final hop enqueued so far: a held one first)
+            if (c->pipe && c->pipe->held.valid) flushHeldFinal(c);
             streamAfter(c->stream, c->finalStream, c->pipeEvent(1));
             if (c->finalStream2) streamAfter(c->stream, c->finalStream2, c->pipeEvent(1));
             if (c->closeStream) streamAfter(c->stream, c->closeStream, c->pipeEvent(3));
@@ -1596,6 +1703,7 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
     }
     if (n == "dense_final") { c->denseFinal = value != 0; return NGX_OK; }
     if (n == "dense_early_loads") { c->denseEarlyLoads = value != 0; return NGX_OK; }
+    if (n == "batch_pair_finals") { c->batchPairFinals = value != 0; return NGX_OK; }
     if (n == "dense_close_total") { c->denseCloseTotal = value != 0; return NGX_OK; }
     if (n == "dense_world_dev") { c->denseWorldDev = value != 0; return NGX_OK; }
     if (n == "dst_replica_max") { c->dstReplicaMax = static_cast<uint64_t>(std::max<int64_t>(value, 0)); return NGX_OK; }
@@ -1721,6 +1829,10 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "dense_finals") *value = static_cast<int64_t>(c->denseFinals);
     else if (n == "dense_early_loads") *value = c->denseEarlyLoads ? 1 : 0;
     else if (n == "dense_early_finals") *value = static_cast<int64_t>(c->denseEarlyFinals);
+    else if (n == "batch_pair_finals") *value = c->batchPairFinals ? 1 : 0;
+    else if (n == "paired_finals") *value = static_cast<int64_t>(c->pairedFinals);
+    else if (n == "jit_dense2_vgprs") *value = c->jit.lastDense2Regs;
+    else if (n == "jit_dense2_scratch") *value = c->jit.lastDense2Scratch;
     else if (n == "dst_replica_max") *value = static_cast<int64_t>(c->dstReplicaMax);
     else if (n == "dst_fetches") *value = static_cast<int64_t>(c->dstFetches);
     else if (n == "dst_fetch_rows") *value = static_cast<int64_t>(c->dstFetchRows);
@@ -3516,13 +3628,60 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
             a.resvTab = resvTable(c, static_cast<uint64_t>(a.resvTB) * a.resvG);
             if (++c->resvSeq == 0) c->resvSeq = 1;
             a.resvSeq = c->resvSeq;
+            // dense (one slot, the grid = the slot's chunks): the loads-first body when the module has it
+            const bool early = kj != nullptr && a.denseMark != nullptr && kj->finalDense != nullptr && c->denseEarlyLoads &&
+                               a.fin == nullptr && a.hs.n == 1;
+            // batch_pair_finals (GoPipe::held): `hold` this launch for the next query, or launch `paired` with the
+            // held one; a held launch that cannot pair with this one goes first, as the single launch it is
+            GoPipe* const PP = c->pipe;
+            const int32_t myIdx = PP && PP->cur ? PP->cur->idx : -1;
+            bool hold = false, paired = false;
+            FinalArgs heldArgs;                                 // paired: the held query's, for its close
+            int heldLane = -1;
+            if (PP && PP->pairFinals) {
+                const bool can = deferrable && early && grid != 0 && kj->finalDense2 != nullptr;
+                if (PP->held.valid && !(can && PP->held.idx + 1 == myIdx && pairable(PP->held, c->parked[PP->held.lane].progLast, a, kj, grid, c->progLast)))
+                    flushHeldFinal(c);
+                paired = PP->held.valid;
+                hold = !paired && can && pairCandidate(PP, myIdx);
+            }
             c->timed("final", (dyn || devE) ? 0 : Ef * (keyReadBytes + kfBytes), [&] {
                 if (grid == 0) return;
-                if (kj) {
+                if (hold) {
+                    HeldFinal& h = PP->held;
+                    h.idx = myIdx;
+                    h.a = a;
+                    h.grid = grid;
+                    h.kj = jk;
+                    h.lane = c->activeLane;
+                    h.fs = c->stream;
+                    h.closeStream = c->closeStream;
+                    h.closePending = c->laneClosePending[c->activeLane];
+                    hipEvent_t& fe = c->heldFrontEv[c->activeLane];
+                    if (!fe) HIP_OK(hipEventCreateWithFlags(&fe, hipEventDisableTiming));
+                    HIP_OK(hipEventRecord(fe, fss.saved));
+                    h.frontEv = fe;
+                    h.valid = true;
+                    c->denseEarlyFinals++;                      // (it runs loads-first, paired or flushed)
+                } else if (paired) {
+                    // this query's final stream (behind its own front stream and lane close: FinalStreamScope) also
+                    // after the held query's front stream, its lane's pending close, and its final stream so far
+                    // (the held query's memsets and uploads of its counters, tables and descriptors went there)
+                    HeldFinal& h = PP->held;
+                    HIP_OK(hipStreamWaitEvent(c->stream, h.frontEv, 0));
+                    if (h.closePending) HIP_OK(hipStreamWaitEvent(c->stream, c->laneCloseEv[h.lane], 0));
+                    if (h.fs != c->stream) streamAfter(c->stream, h.fs, c->pipeEvent(1));
+                    FinalPairArgs pb = FinalPairArgs::of(a);
+                    void* args[] = {&h.a, &pb};
+                    HIP_OK(hipModuleLaunchKernel(kj->finalDense2, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
+                    heldArgs = h.a;
+                    heldLane = h.lane;
+                    h.valid = false;
+                    h.kj.reset();
+                    c->denseEarlyFinals++;
+                    c->pairedFinals++;
+                } else if (kj) {
                     void* args[] = {&a};
-                    // dense (one slot, the grid = the slot's chunks): the loads-first body when the module has it
-                    const bool early = a.denseMark != nullptr && kj->finalDense != nullptr && c->denseEarlyLoads &&
-                                       a.fin == nullptr && a.hs.n == 1;
                     if (early) c->denseEarlyFinals++;
                     HIP_OK(hipModuleLaunchKernel(early ? kj->finalDense : kj->final, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
                 } else if (launchFinal(a, c->stream, grid)) {
@@ -3532,7 +3691,7 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
             // the holes of the groups' last blocks closed, the row count published (also for grid 0). An
             // overlapped final hop's close runs on the close stream: the next query's final hop (another
             // lane's rows and counters) starts on the final stream without waiting for it
-            {
+            if (!hold) {                                        // (a held hop's close follows its launch)
                 hipStream_t fs = c->stream;
                 if (deferrable && c->closeStream) {
                     streamAfter(c->closeStream, fs, c->pipeEvent(4));
@@ -3540,15 +3699,15 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                 }
                 try {
                     c->timed("final_close", 0, [&] {
+                        // paired: the held query's close first (it was enqueued first, it is waited for first)
+                        if (heldLane >= 0 && launchFinalClose(heldArgs, c->stream)) throw Error{NGX_E_DEVICE, "final close"};
                         if (launchFinalClose(a, c->stream)) throw Error{NGX_E_DEVICE, "final close"};
                     });
-                    if (deferrable) {                          // the lane's next final hop waits for this close
-                        hipEvent_t& ev = c->laneCloseEv[c->activeLane];
-                        if (!ev) HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-                        HIP_OK(hipEventRecord(ev, c->stream));
-                        c->laneClosePending[c->activeLane] = true;
-                    }
+                    // the lane's next final hop waits for this close
+                    if (deferrable) recordLaneClose(c, c->activeLane, c->stream);
+                    if (heldLane >= 0) recordLaneClose(c, heldLane, c->stream);
                 } catch (...) {
+                    if (heldLane >= 0) PP->heldFailed = myIdx - 1;   // its close may be missing: it must not wait
                     c->stream = fs;
                     throw;
                 }
@@ -3562,6 +3721,11 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                 uint64_t fin = 0;                               // devE: this hop's packed (|F|, E)
                 const uint64_t* rowsDev = c->resvRows;          // (the next query resets c->resvRows)
                 if (deferrable) goDeferPoint(c);                // ngx_go_batch: the next query runs here
+                // a held final hop is enqueued (paired or flushed) before its query waits for the count
+                if (hold && ((PP->held.valid && PP->held.idx == myIdx) || PP->heldFailed == myIdx)) {
+                    if (PP->held.idx == myIdx) { PP->held.valid = false; PP->held.kj.reset(); }
+                    throw Error{NGX_E_DEVICE, "held final hop was not launched"};
+                }
                 uint64_t nrows = awaitPub(c, rowsPub, rowsDev, &finalErrBits, errFlag, devE ? &fin : nullptr,
                                           devE ? dynTotal : nullptr);
                 haveFinalErrs = true;
@@ -4579,6 +4743,7 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
     // digests need no hold since each lane has its own result rows: a deferred query hashes its rows when it
     // resumes, and no later final hop writes them (the next query on its lane starts after it finished)
     P.holdFinals = false;
+    P.pairFinals = c->batchPairFinals && c->world == 1;
     hipStream_t ctxStream = c->stream;
     try {
         if (c->activeLane != 0) c->useLane(0);
@@ -4616,6 +4781,8 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
         return &j;
     };
     auto resume = [&](GoJob* j) {
+        // a held final hop is enqueued before its query runs on (it waits for the hop's row count)
+        if (P.held.valid && P.held.idx == j->idx) flushHeldFinal(c);
         c->ptraceQuery = j->idx;
         if (c->ptrace) c->pmark("resume");
         c->useLane(j->idx % lanes);
@@ -4625,6 +4792,9 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
         tBatch = &co;
         swapcontext(&P.main, &j->uc);
         P.cur = nullptr;
+        // the second query of a pair is back without having taken the held hop along (it finished or failed
+        // before its final hop, GO_EXIT on an empty frontier among them): the held hop runs alone
+        if (P.held.valid && P.held.idx + 1 == j->idx) flushHeldFinal(c);
         if (c->ptrace) c->pmark("yield " + std::to_string(j->state));
         return j->state;
     };
@@ -4663,6 +4833,7 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
         st = resume(a);
     }
     while (nw) finishOldest();
+    flushHeldFinal(c);                                  // (none is left: every holder was resumed)
     c->pipe = nullptr;
     tDeferFree = false;
     c->finalStream = nullptr;

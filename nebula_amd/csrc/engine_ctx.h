@@ -488,6 +488,13 @@ struct ngx_ctx : LaneState {
     // ahead of the frontier bits (final_kernels.h finalBodyDense; flag dense_early_loads); 0: the generic body
     bool denseEarlyLoads = true;
     uint64_t denseEarlyFinals = 0;                      // launches that took it (flag dense_early_finals, read-only)
+    // ngx_go_batch: queries 2k and 2k + 1 whose dense, loads-first final hops differ only in their frontier run
+    // them as one launch that scans the slot's columns once (final_kernels.h finalBodyDense2; engine.cpp
+    // HeldFinal; flag batch_pair_finals, world 1 only). C2: 0.2198 vs 0.2438 ms per step (tools/ab_batch.py, 100
+    // steps, 8 rounds, ranges apart), the paired launch 417 us for two queries against 2 x 234
+    bool batchPairFinals = true;
+    uint64_t pairedFinals = 0;                          // launches that served two queries (flag paired_finals, read-only)
+    hipEvent_t heldFrontEv[kMaxLanes] = {};             // per lane: its held query's front stream at the hand-off
     uint64_t dstReplicaMax = uint64_t(1) << 30;
     uint64_t dstFetches = 0, dstFetchRows = 0;
     // Also the cleanup of ngx_open's error paths. What is no buffer goes here; the buffers free themselves as the
@@ -503,6 +510,7 @@ struct ngx_ctx : LaneState {
         for (auto e : gbEv) if (e) (void)hipEventDestroy(e);
         for (auto e : pipeEv) if (e) (void)hipEventDestroy(e);
         for (auto e : laneCloseEv) if (e) (void)hipEventDestroy(e);
+        for (auto e : heldFrontEv) if (e) (void)hipEventDestroy(e);
         for (auto e : pipeRing) if (e) (void)hipEventDestroy(e);
         for (auto st : pipeStreams) if (st) (void)hipStreamDestroy(st);
         for (auto st : splitStreams) if (st) (void)hipStreamDestroy(st);

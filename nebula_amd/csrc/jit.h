@@ -26,6 +26,7 @@ struct JitKernels {
     hipFunction_t final = nullptr;      // the fused final-hop kernel (final_kernels.h finalBody)
     hipFunction_t finalDense = nullptr; // eligible shapes (jitDenseEligible): the dense final hop with the edge
                                         // loads ahead of the frontier bits (finalBodyDense); else nullptr
+    hipFunction_t finalDense2 = nullptr; // ... and that scan serving two queries (finalBodyDense2); else nullptr
 };
 
 // one compiled program segment of a query: code[off ...] up to OP_END
@@ -85,6 +86,7 @@ public:
     double compileSeconds = 0;
     int64_t lastRegs = -1, lastScratch = -1;    // hipFuncGetAttribute of the last compiled kernel
     int64_t lastDenseRegs = -1, lastDenseScratch = -1;   // ... and of its module's ngx_jit_final_dense (-1: none)
+    int64_t lastDense2Regs = -1, lastDense2Scratch = -1; // ... and of its ngx_jit_final_dense2 (-1: none)
     size_t capacity = 64;
     bool async = false;
     int device = 0;                             // HIP device the background thread loads modules on
@@ -93,7 +95,7 @@ public:
 private:
     struct Entry { std::shared_ptr<JitKernels> k; uint64_t used = 0; };
     std::vector<hipModule_t> retired_;
-    struct Done { std::string shape; JitKernels k; std::string err; double seconds; int64_t regs[4]; };   // regs, scratch; dense
+    struct Done { std::string shape; JitKernels k; std::string err; double seconds; int64_t regs[6]; };   // regs, scratch; dense; dense2
     void admit();                               // finished background compiles -> cache_ / failures_
     void insert(const std::string& shape, const JitKernels& k);
     uint64_t tick_ = 0;

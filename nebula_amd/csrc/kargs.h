@@ -41,6 +41,8 @@ struct OutCol {
 constexpr int kJitConsts = 24;          // PUSH literals a generated kernel reads from its arguments
 constexpr int kInlineCols = 12;         // result column descriptors passed in the arguments themselves
 
+// A field added here is either shared by the two queries of a paired dense final hop or a query's own: add it
+// to engine.cpp pairable() (compared) or to FinalPairArgs::of / view below (carried per query).
 struct FinalArgs {
     const uint32_t* F;                  // frontier rows
     const uint64_t* estart;             // exclusive prefix of entry degrees, [nEnt] = E
@@ -108,6 +110,61 @@ struct FinalArgs {
     // only when its row's mark is denseEp (the frontier the compaction would have listed). null: off
     const uint8_t* denseMark;
     uint32_t denseEp;
+};
+
+// The second query of a paired dense final hop (final_kernels.h finalBodyDense2): two FinalArgs by value
+// exceed the 4 KiB of kernel arguments, so the second query passes only what is its own (frontier marks,
+// reservation state, outputs, error and publication words); slot, columns, literals, widths and the
+// reservation geometry are the first query's (engine.cpp pairable). view() is its FinalArgs.
+struct FinalPairArgs {
+    const uint8_t* denseMark;
+    uint32_t denseEp;
+    uint32_t resvTB;
+    uint32_t resvSeq;
+    uint64_t* resvTab;
+    uint64_t* resvCtl;
+    uint64_t* resvNext;
+    uint64_t oBase;
+    int64_t* oSrc;
+    int64_t* oDst;
+    int64_t* oRank;
+    int32_t* oType;
+    const OutCol* oCols;
+    OutCol oColsIn[kInlineCols];
+    uint32_t* err;
+    uint64_t* rowsPub;
+    uint64_t rowsSeq;
+    const uint64_t* dynTotal;
+    const uint64_t* dynTiles;
+    uint64_t nDynTiles;
+
+    __host__ __device__ static FinalPairArgs of(const FinalArgs& q) {
+        FinalPairArgs p;
+        p.denseMark = q.denseMark; p.denseEp = q.denseEp;
+        p.resvTB = q.resvTB; p.resvSeq = q.resvSeq;
+        p.resvTab = q.resvTab; p.resvCtl = q.resvCtl; p.resvNext = q.resvNext;
+        p.oBase = q.oBase;
+        p.oSrc = q.oSrc; p.oDst = q.oDst; p.oRank = q.oRank; p.oType = q.oType;
+        p.oCols = q.oCols;
+        for (int y = 0; y < kInlineCols; y++) p.oColsIn[y] = q.oColsIn[y];
+        p.err = q.err; p.rowsPub = q.rowsPub; p.rowsSeq = q.rowsSeq;
+        p.dynTotal = q.dynTotal; p.dynTiles = q.dynTiles; p.nDynTiles = q.nDynTiles;
+        return p;
+    }
+    // `shared` with this query's own fields in place of its
+    __host__ __device__ FinalArgs view(const FinalArgs& shared) const {
+        FinalArgs q = shared;
+        q.denseMark = denseMark; q.denseEp = denseEp;
+        q.resvTB = resvTB; q.resvSeq = resvSeq;
+        q.resvTab = resvTab; q.resvCtl = resvCtl; q.resvNext = resvNext;
+        q.oBase = oBase;
+        q.oSrc = oSrc; q.oDst = oDst; q.oRank = oRank; q.oType = oType;
+        q.oCols = oCols;
+        for (int y = 0; y < kInlineCols; y++) q.oColsIn[y] = oColsIn[y];
+        q.err = err; q.rowsPub = rowsPub; q.rowsSeq = rowsSeq;
+        q.dynTotal = dynTotal; q.dynTiles = dynTiles; q.nDynTiles = nDynTiles;
+        return q;
+    }
 };
 
 // rows a GO final launch may leave past its row count before k_final_close (outputs are sized for them)
