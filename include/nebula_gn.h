@@ -936,6 +936,11 @@ int32_t ngx_kernel_stats(ngx_ctx* ctx, const ngx_kernel_stat** out, int32_t* n);
  *          writes both queries' rows; any other second query makes the first one's final hop run alone, as
  *          with 0. Same results. Read-only "paired_finals" (launches that served two queries),
  *          "jit_dense2_vgprs" / "jit_dense2_scratch" (that kernel's registers and scratch).
+ *   "batch_final_turns"  1 (default) / 0: in a pipelined ngx_go_batch at world 1 with two final streams, every
+ *          final-hop launch (a single hop, a pair, a held hop launched alone) goes to the final stream the launch
+ *          before it did not use; 0: query i's launch on final stream i & 1, which with batch_pair_finals puts
+ *          every pair and its closes on the second stream. Same results. Read-only "final_launches_s0" /
+ *          "final_launches_s1": the final-hop launches enqueued on each final stream.
  *   "final_nt_loads" / "final_nt_stores"  0 (default) / 1: the generated GO final hop loads its columns /
  *          stores its rows non-temporally (not kept in L2). Same results.
  * Read-only counters for ngx_get_flag: "jit_compiled", "jit_hits", "jit_failed", "jit_compile_us",

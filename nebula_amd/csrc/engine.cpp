@@ -154,6 +154,12 @@ struct GoPipe {
     const ngx_go_plan* const* plans = nullptr;
     int32_t n = 0;
     bool pairFinals = false;                           // flag batch_pair_finals at world 1
+    // flag batch_final_turns at world 1 with two final streams: every final-hop launch takes the final stream
+    // the launch before it did not use (ngx_ctx::finalTurn). A holder takes its turn when it holds; the pair
+    // kernel and both closes (or the flushed single launch) run on that stream, h.fs. The holder's partner
+    // prepares its launch on h.fs too (FinalStreamScope), so its waits and memsets are already where the pair
+    // launches; if it cannot pair after all it moves to the other stream, behind them, before the flush
+    bool finalTurns = false;
     HeldFinal held;
     int32_t heldFailed = -1;                           // the query whose held launch (or its close) failed to enqueue
 };
@@ -829,6 +835,7 @@ void flushHeldFinal(ngx_ctx* c) {
     try {
         void* args[] = {&h.a};
         HIP_OK(hipModuleLaunchKernel(h.kj->finalDense, h.grid, 1, 1, 256u, 1, 1, 0, h.fs, args, nullptr));
+        c->countFinalLaunch(h.fs);
         hipStream_t cs = h.fs;
         if (h.closeStream) {
             streamAfter(h.closeStream, h.fs, c->pipeEvent(4));
@@ -895,6 +902,13 @@ struct FinalStreamScope {
         if (!c->finalStream) return;
         if (onFinal) {
             hipStream_t fs = c->finalCur ? c->finalCur : c->finalStream;
+            const GoPipe* P = c->pipe;
+            if (P && P->finalTurns) {
+                // the stream whose turn it is; the partner of a held hop prepares on the holder's stream, where
+                // the pair would launch (the holder took that turn)
+                const bool partner = P->held.valid && P->cur && P->held.idx + 1 == P->cur->idx;
+                fs = partner ? P->held.fs : c->turnStream();
+            }
             streamAfter(fs, c->stream, c->pipeEvent(0));
             if (c->laneClosePending[c->activeLane]) HIP_OK(hipStreamWaitEvent(fs, c->laneCloseEv[c->activeLane], 0));
             saved = c->stream;
@@ -1704,6 +1718,7 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
     if (n == "dense_final") { c->denseFinal = value != 0; return NGX_OK; }
     if (n == "dense_early_loads") { c->denseEarlyLoads = value != 0; return NGX_OK; }
     if (n == "batch_pair_finals") { c->batchPairFinals = value != 0; return NGX_OK; }
+    if (n == "batch_final_turns") { c->batchFinalTurns = value != 0; return NGX_OK; }
     if (n == "dense_close_total") { c->denseCloseTotal = value != 0; return NGX_OK; }
     if (n == "dense_world_dev") { c->denseWorldDev = value != 0; return NGX_OK; }
     if (n == "dst_replica_max") { c->dstReplicaMax = static_cast<uint64_t>(std::max<int64_t>(value, 0)); return NGX_OK; }
@@ -1831,6 +1846,9 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "dense_early_finals") *value = static_cast<int64_t>(c->denseEarlyFinals);
     else if (n == "batch_pair_finals") *value = c->batchPairFinals ? 1 : 0;
     else if (n == "paired_finals") *value = static_cast<int64_t>(c->pairedFinals);
+    else if (n == "batch_final_turns") *value = c->batchFinalTurns ? 1 : 0;
+    else if (n == "final_launches_s0") *value = static_cast<int64_t>(c->finalLaunches[0]);
+    else if (n == "final_launches_s1") *value = static_cast<int64_t>(c->finalLaunches[1]);
     else if (n == "jit_dense2_vgprs") *value = c->jit.lastDense2Regs;
     else if (n == "jit_dense2_scratch") *value = c->jit.lastDense2Scratch;
     else if (n == "dst_replica_max") *value = static_cast<int64_t>(c->dstReplicaMax);
@@ -3640,8 +3658,18 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
             int heldLane = -1;
             if (PP && PP->pairFinals) {
                 const bool can = deferrable && early && grid != 0 && kj->finalDense2 != nullptr;
-                if (PP->held.valid && !(can && PP->held.idx + 1 == myIdx && pairable(PP->held, c->parked[PP->held.lane].progLast, a, kj, grid, c->progLast)))
+                if (PP->held.valid && !(can && PP->held.idx + 1 == myIdx && pairable(PP->held, c->parked[PP->held.lane].progLast, a, kj, grid, c->progLast))) {
+                    // batch_final_turns: this query prepared on the holder's stream (FinalStreamScope). The held
+                    // hop runs there alone; this one takes the other stream, behind what it has enqueued so far
+                    // (its front-stream and lane-close waits, its counters' and tables' memsets)
+                    hipStream_t mine = c->stream;
+                    if (PP->finalTurns && deferrable && c->stream == PP->held.fs && c->turnStream() != c->stream) {
+                        mine = c->turnStream();
+                        streamAfter(mine, c->stream, c->pipeEvent(1));
+                    }
                     flushHeldFinal(c);
+                    c->stream = mine;
+                }
                 paired = PP->held.valid;
                 hold = !paired && can && pairCandidate(PP, myIdx);
             }
@@ -3662,11 +3690,14 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                     HIP_OK(hipEventRecord(fe, fss.saved));
                     h.frontEv = fe;
                     h.valid = true;
+                    if (PP->finalTurns) c->finalTurn ^= 1;      // holding is its turn: the launch will be on h.fs
                     c->denseEarlyFinals++;                      // (it runs loads-first, paired or flushed)
                 } else if (paired) {
                     // this query's final stream (behind its own front stream and lane close: FinalStreamScope) also
                     // after the held query's front stream, its lane's pending close, and its final stream so far
-                    // (the held query's memsets and uploads of its counters, tables and descriptors went there)
+                    // (the held query's memsets and uploads of its counters, tables and descriptors went there).
+                    // batch_final_turns: this stream is the holder's (h.fs), which has all of these waits already;
+                    // the two waits below repeat the holder's own and cost nothing
                     HeldFinal& h = PP->held;
                     HIP_OK(hipStreamWaitEvent(c->stream, h.frontEv, 0));
                     if (h.closePending) HIP_OK(hipStreamWaitEvent(c->stream, c->laneCloseEv[h.lane], 0));
@@ -3674,6 +3705,7 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                     FinalPairArgs pb = FinalPairArgs::of(a);
                     void* args[] = {&h.a, &pb};
                     HIP_OK(hipModuleLaunchKernel(kj->finalDense2, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
+                    c->countFinalLaunch(c->stream);
                     heldArgs = h.a;
                     heldLane = h.lane;
                     h.valid = false;
@@ -3686,6 +3718,10 @@ int32_t runGo(ngx_ctx* c, Space& sp, const ngx_go_plan& p, GoResultHolder& R, co
                     HIP_OK(hipModuleLaunchKernel(early ? kj->finalDense : kj->final, grid, 1, 1, nt, 1, 1, 0, c->stream, args, nullptr));
                 } else if (launchFinal(a, c->stream, grid)) {
                     throw Error{NGX_E_DEVICE, "final"};
+                }
+                if (!hold && !paired && deferrable && c->finalStream) {   // a single launch on a final stream: its turn
+                    c->countFinalLaunch(c->stream);
+                    if (PP && PP->finalTurns) c->finalTurn ^= 1;
                 }
             });
             // the holes of the groups' last blocks closed, the row count published (also for grid 0). An
@@ -4764,6 +4800,8 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
     // hop on that hop's stream
     c->finalStream2 = c->batchFinals == 2 ? roles[3] : nullptr;
     if (c->finalStream2) c->closeStream = nullptr;
+    P.finalTurns = c->batchFinalTurns && c->world == 1 && c->finalStream2 != nullptr;
+    c->finalTurn = 0;                                   // every batch starts on the first final stream
     BatchCo co{c, &P, digests != nullptr};
     // query i runs on lane i % lanes with the coroutine stack of that lane; up to lanes - 1 queries wait at
     // their deferral point (holding finals: one)
@@ -4787,7 +4825,8 @@ extern "C" int32_t ngx_go_batch(ngx_ctx* c, const ngx_go_plan* const* plans, int
         if (c->ptrace) c->pmark("resume");
         c->useLane(j->idx % lanes);
         c->stream = roles[c->pipeFronts == 2 && (j->idx & 1) ? 2 : 0];   // query i's hops: front i % fronts
-        c->finalCur = (c->finalStream2 && (j->idx & 1)) ? c->finalStream2 : c->finalStream;   // its final hop
+        // its final hop (batch_final_turns 0; with 1 FinalStreamScope takes the stream whose turn it is)
+        c->finalCur = (c->finalStream2 && (j->idx & 1)) ? c->finalStream2 : c->finalStream;
         P.cur = j;
         tBatch = &co;
         swapcontext(&P.main, &j->uc);

@@ -495,6 +495,19 @@ struct ngx_ctx : LaneState {
     bool batchPairFinals = true;
     uint64_t pairedFinals = 0;                          // launches that served two queries (flag paired_finals, read-only)
     hipEvent_t heldFrontEv[kMaxLanes] = {};             // per lane: its held query's front stream at the hand-off
+    // two final streams: each final-hop launch of a batch (a single hop, a pair, a flushed held hop) goes to the
+    // final stream the launch before it did not use (engine.cpp FinalStreamScope; flag batch_final_turns, world 1
+    // only). 0: query i's on final stream i & 1, which with pairing on puts every pair kernel and both its closes
+    // on the second stream (the pair is launched by its odd query), one behind the other. C2: 0.2088 vs 0.2289
+    // ms per step (tools/ab_batch.py, 100 steps, 8 rounds, ranges apart; profiles/r12_turns_summary.md)
+    bool batchFinalTurns = true;
+    int finalTurn = 0;                                  // the final stream (0 / 1) the batch's next launch takes
+    uint64_t finalLaunches[2] = {0, 0};                 // final-hop launches enqueued per final stream (final_launches_s0 / _s1)
+    hipStream_t turnStream() const { return finalTurn && finalStream2 ? finalStream2 : finalStream; }
+    void countFinalLaunch(hipStream_t s) {
+        if (s && s == finalStream) finalLaunches[0]++;
+        else if (s && s == finalStream2) finalLaunches[1]++;
+    }
     uint64_t dstReplicaMax = uint64_t(1) << 30;
     uint64_t dstFetches = 0, dstFetchRows = 0;
     // Also the cleanup of ngx_open's error paths. What is no buffer goes here; the buffers free themselves as the
