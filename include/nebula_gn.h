@@ -773,6 +773,45 @@ typedef struct {
 int32_t ngx_lookup(ngx_ctx* ctx, const ngx_lookup_plan* plan, ngx_lookup_result** out);
 void ngx_lookup_result_free(ngx_lookup_result* r);
 
+/* ---------------------------------------------------------------- | YIELD ... [WHERE ...] over a GO result */
+/* `GO ... | YIELD <columns> [WHERE <expr>]` with the filter, the projection and the aggregates on the device: replaces
+ * YieldExecutor::executeInputs (src/graph/YieldExecutor.cpp:171-279; the functions of src/graph/AggregateFunction.h)
+ * for a result that stayed in HBM. Only the kept rows' cells, or the one aggregate row, cross PCIe. `r` is a
+ * result_on_device result of this context, and the call comes before any other call on the context (as
+ * ngx_go_group_by). input_names are r's YIELD column names: the `$-` schema the expressions are compiled against;
+ * where and every yield's expr are Expression::encode bytes.
+ *   projection  no yield has a function: per row WHERE keeps, in the order of the rows in r, one output row. A bare
+ *               `$-.col` is copied at its stored width under r's column type (any static type, STRING included);
+ *               an expression's value takes the type it has on the first input row (INT, DOUBLE or BOOL; a cast's
+ *               target type, a relational or logical expression BOOL).
+ *   aggregates  some yield has a function: one output row. The value types come from the first input row, kept or
+ *               not, as the reference's output schema does; the results per function and type are ngx_go_group_by's
+ *               (integer sums wrap; a VID sum keeps its type; AVG is of INT / DOUBLE; BIT_* of a non-INT value is
+ *               0; MAX / MIN not of BOOL / STRING; double SUM / AVG depend on the order of the additions). A yield
+ *               without a function that is no bare input column (NGX_AGG_GROUP) holds its value on the last kept row.
+ *               Rows in, none kept: still one row (COUNT 0, SUM 0, AVG 0 / 0).
+ * No input rows: nothing is launched and nrows is 0 in both forms.
+ * NGX_E_UNSUPPORTED with a reason starting "yield:" (ngx_last_error), decided before any row is returned, for:
+ * world > 1, 2^32 rows or more, more than 64 yields, an UNKNOWN-typed (per-row type) or FLOAT column an expression
+ * reads, an expression whose value is a string (a bare STRING column is fine, and so is COUNT of a constant),
+ * COUNT_DISTINCT and STD, whatever the expression compiler refuses, a TIMESTAMP value or a bare input column without
+ * function beside an aggregate, MAX / MIN / a function-less yield with no row kept (the reference fails these
+ * sentences), and any row whose WHERE or yield evaluation fails or changes type ("yield: an expression failed on a
+ * row"). The caller then runs the host restatement (nebula_amd/yieldexec.py), which words the reference's Status.
+ * Flags: "yield_device" (read-only) counts the calls completed on the device; "yield_grid_max" (0, the default:
+ * built-in 1024, else 1 .. 1024) caps the workgroups of every kernel, so a test can make one workgroup sweep every
+ * row: same rows in the same order under every setting. ngx_kernel_stats: launch groups "yield_keep", "yield_scan",
+ * "yield_emit", "yield_agg". */
+typedef struct { int32_t fn;                 /* NGX_AGG_*; NGX_AGG_GROUP: no function */
+                 const uint8_t* expr; uint32_t expr_len; } ngx_yield_col;   /* Expression::encode bytes */
+typedef struct { int32_t ncols_in; const char* const* input_names;          /* the $- schema: r's YIELD names */
+                 const uint8_t* where; uint32_t where_len;                  /* 0: none */
+                 int32_t nyields; const ngx_yield_col* yields; } ngx_yield_plan;
+typedef struct { int32_t code, ncols; const int32_t* col_types; uint64_t nrows, input_rows, kept_rows;
+                 const ngx_cell* cells; const char* strings; uint64_t strings_len; double device_ms; } ngx_yield_result;
+int32_t ngx_go_yield(ngx_ctx*, const ngx_go_result* r, const ngx_yield_plan*, ngx_yield_result** out);
+void ngx_yield_result_free(ngx_yield_result*);
+
 /* ---------------------------------------------------------------- FIND SHORTEST PATH
  * `FIND SHORTEST PATH FROM <vids> TO <vids> OVER <edges> [REVERSELY] [UPTO n STEPS]` (FindPathExecutor,
  * src/graph/FindPathExecutor.cpp) searched in HBM: breadth-first levels from the sources over the sentence's edge

@@ -1775,6 +1775,12 @@ int32_t ngx_set_flag(ngx_ctx* c, const char* name, int64_t value) {
         c->lookupGridMax = static_cast<uint32_t>(value);
         return NGX_OK;
     }
+    if (n == "yield_grid_max") {
+        if (value < 0 || value > static_cast<int64_t>(kYieldGridMax))
+            return fail(c, NGX_E_BAD_ARGUMENT, "yield_grid_max: 0 (built-in) or 1 .. " + std::to_string(kYieldGridMax));
+        c->yieldGridMax = static_cast<uint32_t>(value);
+        return NGX_OK;
+    }
     if (n == "lookup_rows_max") {
         if (value < 0) return fail(c, NGX_E_BAD_ARGUMENT, "lookup_rows_max: >= 0");
         c->lookupRowsMax = value;
@@ -1896,6 +1902,8 @@ int32_t ngx_get_flag(ngx_ctx* c, const char* name, int64_t* value) {
     else if (n == "lookup_grid_max") *value = c->lookupGridMax;
     else if (n == "lookup_rows_max") *value = c->lookupRowsMax;
     else if (n == "lookup_device") *value = static_cast<int64_t>(c->lookupDevice);
+    else if (n == "yield_grid_max") *value = c->yieldGridMax;
+    else if (n == "yield_device") *value = static_cast<int64_t>(c->yieldDevice);
     else if (n == "set_loop_flushes") *value = static_cast<int64_t>(c->setLoopFlushes);
     else if (n == "group_grid_max") *value = c->groupGridMax;
     else if (n == "order_grid_max") *value = c->orderGridMax;

@@ -9,6 +9,7 @@
 // op_fetch.cpp       FETCH PROP ON
 // op_lookup.cpp      LOOKUP ON
 // op_findpath.cpp    FIND SHORTEST PATH
+// op_yield.cpp       | YIELD ... [WHERE ...]
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -314,6 +315,12 @@ struct ngx_ctx : LaneState {
     uint64_t lookupDevice = 0;                          // calls completed (flag lookup_device)
     uint32_t lookupGridMax = 0;                         // flag lookup_grid_max: most workgroups of a sweep, 0: built-in
     int64_t lookupRowsMax = int64_t(1) << 26;           // flag lookup_rows_max: the most output rows
+    // ngx_go_yield: the keep bitmap; per 256-row chunk the kept rows and their scan; column and yield descriptors,
+    // programs and their constant strings; state words, error words and probed values; string lengths and their
+    // scan; output cells and bytes
+    DBuf yKeep, yCount, yBase, yTiles, yDesc, yCode, yPool, yState, ySlen, ySpre, yCells, yStr;
+    uint64_t yieldDevice = 0;                           // calls completed on the device (flag yield_device)
+    uint32_t yieldGridMax = 0;                          // flag yield_grid_max: most workgroups of a sweep, 0: built-in
     // ngx_go_set: the string arenas of the left traversal while the right one runs on the second lane
     std::vector<DBuf> setArena;
     // flag set_check_left (debug): ngx_go_set digests the left result before and after the right traversal

@@ -787,6 +787,68 @@ struct LookupArgs {
 int launchLookupKeep(const LookupArgs& a, hipStream_t s);
 int launchLookupEmit(const LookupArgs& a, hipStream_t s);
 
+// `| YIELD <columns> [WHERE <expr>]` over a device-resident result (yield.hip; ngx_go_yield). Every kernel sweeps
+// 256 rows a workgroup and turn, so rows keep their order under every grid size:
+//   keep   a thread per row evaluates WHERE (vmEval<true>); the wave's ballot is one word of the keep bitmap (a word
+//          per 64 rows), the popcounts of a 256-row chunk its count. No WHERE: not launched, keepBits is null and
+//          every row is kept.
+//   emit   (projection) a kept row's output index is base[chunk] + the kept rows before it in the chunk
+//          (launchScanU64 over the chunk counts); a yield is a column copied at its stored width or a program's value.
+//          Run twice when a yield is a STRING column (lengths, then cells), as LOOKUP's emit.
+//   agg    (aggregates) per kept row every yield's value goes into its state words: reduced across the wave's lanes,
+//          across the workgroup's waves in LDS, then one 64-bit atomic per workgroup and word.
+//   probe  one thread evaluates every program on one row: the first input row types the columns, the last kept
+//          row gives a function-less expression its value.
+// An evaluation that fails sets err[0] bit 0, a value of another type than the first row's bit 1; err[1] is the
+// VM's host-only mark (VmEnv::unsupported).
+constexpr int kYieldMax = 64;                       // yield columns
+constexpr uint32_t kYieldGridMax = 1024;
+enum { kYieldCol = 0, kYieldEval, kYieldNone };     // a column's copy, a program's value, not evaluated (COUNT of a constant)
+enum { kYieldSrcOne = 0, kYieldSrcValue, kYieldSrcOrdered, kYieldSrcRow };   // 1, the value, its order key (double), row + 1
+struct YieldItem {
+    int32_t mode;                       // kYield*
+    int32_t a;                          // kYieldCol: the column; kYieldEval: the program's first Insn in code
+    int32_t cell;                       // projection: NGX_CELL_* of the output cell
+    int32_t vt;                         // kYieldEval: the V_* every kept row's value has
+    uint64_t poolOff;                   // kYieldEval: the program's constant strings in pool
+};
+struct YieldSlot {
+    int32_t op;                         // kGroup* (groupby.hip's state operators)
+    int32_t src;                        // kYieldSrc*
+    int32_t y;                          // the yield whose value it takes
+    int32_t pad;
+};
+struct YieldProbe {
+    int64_t x;
+    uint32_t len;
+    uint32_t vt;                        // V_*; V_ERR: the evaluation failed
+};
+struct YieldArgs {
+    uint64_t n;
+    const DResultCol* cols;             // device array: every column of the result
+    const Insn* code;                   // the programs, each ending in OP_END
+    const char* pool;
+    int32_t whereOff;                   // keep: WHERE's first Insn
+    int32_t ny, nslots;
+    uint64_t wherePool;
+    const YieldItem* items;             // device arrays
+    const YieldSlot* slots;             // ordered by y
+    uint64_t* keepBits;                 // a word per 64 rows; null: every row kept
+    uint64_t* chunkCount;               // keep: kept rows per 256-row chunk
+    const uint64_t* chunkBase;          // emit with keepBits: exclusive scan of chunkCount
+    uint64_t* lenOut;                   // emit, length pass: per output row its string bytes; null: the cell pass
+    const uint64_t* strPre;             // cell pass: exclusive scan of the lengths; null: no string yields
+    char* strOut;
+    GroupCell* cells;                   // m * ny
+    uint64_t* state;                    // agg: nslots words, initialised by the launcher
+    uint32_t* err;                      // two words, zeroed by the caller
+    uint32_t gridMax;                   // most workgroups of a sweep (flag yield_grid_max); 0: kYieldGridMax
+};
+int launchYieldKeep(const YieldArgs& a, hipStream_t s);
+int launchYieldEmit(const YieldArgs& a, hipStream_t s);
+int launchYieldAgg(const YieldArgs& a, hipStream_t s);
+int launchYieldProbe(const YieldArgs& a, uint64_t row, YieldProbe* out, hipStream_t s);
+
 // Batched device -> host copy by a kernel: every array is streamed with 16-byte loads and stores into
 // page-locked host memory mapped into the device address space (dst = hipHostGetDevicePointer), so
 // the copy runs at the PCIe write rate on all CUs instead of on one DMA engine.

@@ -25,6 +25,17 @@ struct DInputCol {
     const uint8_t* t;
 };
 
+// a column of a device-resident result as an expression over its rows reads it (vmEval<true>: OP_INPUT takes
+// column a of row EdgeCtx::pos): the array at its stored width (1 / 2 / 4 signed, 8; 0: no array, every row
+// holds konst), the lengths of a string column (x holds 8-byte device pointers), the V_* of every row
+struct DResultCol {
+    const void* x;
+    const uint32_t* len;
+    int64_t konst;
+    int32_t w;
+    int32_t vt;
+};
+
 // per-edge flags (HostSlot::eflags)
 enum : uint8_t {
     EF_EMPTY_VALUE = 1,    // the KV value was empty: no RowReader, filter not evaluated (.inl:520)
@@ -91,7 +102,8 @@ enum Op : uint8_t {
     OP_LT, OP_LE, OP_GT, OP_GE, OP_EQ, OP_NE, OP_CONTAINS,
     OP_AND, OP_OR, OP_LXOR,
     OP_FUNC,           // a = function id, b = argc, mode = builder buffer (kNoBuf: none)
-    OP_INPUT,          // $-.x / $var.x of the edge's input row (multi-root pipe walks): a = input column
+    OP_INPUT,          // $-.x / $var.x of the edge's input row (multi-root pipe walks): a = input column;
+                       // vmEval<true> (yield.hip): column a of a device-resident result's row (DResultCol)
 };
 
 enum Func : int32_t {

@@ -716,7 +716,17 @@ __device__ __forceinline__ Val opInput(const VmEnv& env, const EdgeCtx& ec, int3
     return Val{gld<int64_t>(c.x, ec.in), gld<uint32_t>(c.len, ec.in), gld<uint8_t>(c.t, ec.in)};
 }
 
+// $-.x over a device-resident result (vmEval<true>): env.input points at DResultCol descriptors, ec.pos is the row
+__device__ __forceinline__ Val opResultCol(const VmEnv& env, const EdgeCtx& ec, int32_t col) {
+    const DResultCol& c = reinterpret_cast<const DResultCol*>(env.input)[col];
+    const int64_t x = c.w ? loadW(c.x, c.w, ec.pos) : c.konst;
+    return Val{x, c.vt == V_STR && c.len != nullptr ? gld<uint32_t>(c.len, ec.pos) : 0u, static_cast<uint8_t>(c.vt)};
+}
+
 // ------------------------------------------------------------------------------ interpreter
+// RESULT: OP_INPUT reads a device-resident result's columns (opResultCol) instead of a pipe's input table; the
+// GO kernels instantiate <false>, whose code holds nothing of the other getter
+template <bool RESULT = false>
 static __device__ __noinline__ Val vmEval(const Insn* code, const VmEnv& env, const EdgeCtx& ec, char* sout = nullptr) {
     Val st[kMaxStack];
     char sbuf[kMaxStrBuilds][kStrBuildBytes];
@@ -731,7 +741,10 @@ static __device__ __noinline__ Val vmEval(const Insn* code, const VmEnv& env, co
             case OP_ECOL: st[sp++] = opEcol(env, ec, in.a, in.b, in.mode, constVal(in.t2, in.imm, 0, env.pool)); break;
             case OP_EKEY: st[sp++] = opEkey(ec, in.a, in.b, in.mode, constVal(in.t2, in.imm, 0, env.pool)); break;
             case OP_EDST: st[sp++] = opEdst(ec, in.b); break;
-            case OP_INPUT: st[sp++] = opInput(env, ec, in.a); break;
+            case OP_INPUT:
+                if constexpr (RESULT) st[sp++] = opResultCol(env, ec, in.a);
+                else st[sp++] = opInput(env, ec, in.a);
+                break;
             case OP_SRCTAG: case OP_DSTTAG:
                 st[sp++] = opTag(env, in.op == OP_SRCTAG ? ec.srow : ec.drow, in.a, in.b, in.mode,
                                  constVal(in.t2, in.imm, 0, env.pool), in.op == OP_DSTTAG);

@@ -305,6 +305,30 @@ class LookupSpec:
     types: List[int]
 
 
+class YieldColC(ctypes.Structure):
+    _fields_ = [("fn", c_i32), ("expr", ctypes.c_char_p), ("expr_len", c_u32)]
+
+
+class YieldPlanC(ctypes.Structure):
+    _fields_ = [("ncols_in", c_i32), ("input_names", P(ctypes.c_char_p)), ("where", ctypes.c_char_p),
+                ("where_len", c_u32), ("nyields", c_i32), ("yields", P(YieldColC))]
+
+
+class YieldResultC(ctypes.Structure):
+    _fields_ = [("code", c_i32), ("ncols", c_i32), ("col_types", P(c_i32)), ("nrows", c_u64), ("input_rows", c_u64),
+                ("kept_rows", c_u64), ("cells", P(Cell)), ("strings", ctypes.c_void_p), ("strings_len", c_u64),
+                ("device_ms", c_dbl)]
+
+
+@dataclass
+class YieldSpec:
+    """ngx_yield_plan: the `$-` schema (the GO's YIELD column names), WHERE's Expression::encode bytes (None: no
+    WHERE) and per yield column its function name ("" for none) and its expression's bytes."""
+    input_names: List[str]
+    where: Optional[bytes]
+    yields: List[Tuple[str, bytes]]
+
+
 class Stat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("value", c_i64)]
 
@@ -348,6 +372,8 @@ SIGNATURES = {
     "ngx_fetch_result_free": (None, [P(FetchResultC)]),
     "ngx_lookup": (c_i32, [ctypes.c_void_p, P(LookupPlanC), P(P(LookupResultC))]),
     "ngx_lookup_result_free": (None, [P(LookupResultC)]),
+    "ngx_go_yield": (c_i32, [ctypes.c_void_p, P(GoResultC), P(YieldPlanC), P(P(YieldResultC))]),
+    "ngx_yield_result_free": (None, [P(YieldResultC)]),
     "ngx_find_path": (c_i32, [ctypes.c_void_p, P(PathPlanC), P(P(PathResultC))]),
     "ngx_path_result_free": (None, [P(PathResultC)]),
     "ngx_stats": (c_i32, [ctypes.c_void_p, P(P(Stat)), P(c_i32)]),
@@ -483,6 +509,10 @@ class GoResult:
     path_found: int = 0                  # find_path: bit j set when target j was found (ngx_path_result.found)
     tags_seen: int = 0                   # fetch: bit t set when some key had a row of the plan's tag t
     keep_bytes: int = 0                  # lookup: bytes the keep pass had to read
+    # yield_by: the sentence's device time, and the rows WHERE kept (go_* as for group_by)
+    yield_device_ms: float = 0.0
+    kept_rows: int = 0
+    yield_cells: object = None           # yield_by with rows=False: the cells as a numpy (nrows, ncols) record array
 
 
 @dataclass
@@ -524,6 +554,7 @@ class Engine:
     device_group_by = True                     # go(..., group_by=...) groups a device-resident result (pipeline.py)
     device_order_by = True                     # go(..., order_by=...) selects a device-resident result's top rows
     device_group_order = True                  # go(..., group_by=..., order_by=...) does both in HBM in one call
+    device_yield = True                        # go_yield: `GO | YIELD ... [WHERE ...]` filtered / reduced in HBM
     device_set_op = True                       # go_set(left, right, op) runs both GOs and the set operator in HBM
     device_find_path = True                    # find_path(space, sentence) searches FIND SHORTEST PATH in HBM
     path_paths_max = 1 << 20                   # find_path: FIND ALL / NOLOOP PATH answers with more walks are refused ("find path: more than ... paths")
@@ -696,7 +727,8 @@ class Engine:
            raise_on_error: bool = False, rows: bool = True, on_device: bool = False, fetch: bool = False,
            columnar: bool = False, digest_fn=None, arrays: bool = True, input=None,
            yield_only: bool = False, compact: bool = False, device_digest: bool = False,
-           group_by: Optional[GroupBySpec] = None, order_by: Optional[OrderBySpec] = None) -> GoResult:
+           group_by: Optional[GroupBySpec] = None, order_by: Optional[OrderBySpec] = None,
+           yield_by: Optional[YieldSpec] = None) -> GoResult:
         """Run one GO. rows=False skips decoding cells into Python tuples; on_device=True leaves the
         result rows in HBM (GoResult.nrows and the statistics only); with fetch=True the HBM arrays
         (src/dst/rank/type and the columnar YIELD columns) are copied back into the result.
@@ -719,8 +751,10 @@ class Engine:
         device_ms / order_device_ms the selection's, order_host_sort_ms the library's sort of the winners.
         group_by and order_by together: the group rows are ordered and cut in HBM too (ngx_go_group_order_by;
         the spec's factors name yield columns of group_by); rows / nrows / col_types describe the window of
-        group rows, device_ms / group_device_ms / order_device_ms are the one call's time."""
-        if group_by is not None or order_by is not None:
+        group rows, device_ms / group_device_ms / order_device_ms are the one call's time.
+        yield_by: likewise, the `| YIELD ... [WHERE ...]` sentence behind the GO runs over its rows in HBM
+        (ngx_go_yield, go_yield below)."""
+        if group_by is not None or order_by is not None or yield_by is not None:
             on_device, columnar = True, False
         if isinstance(s, PreparedGo):                       # its own pushdown / result-placement flags
             plan, keep = s.plan, s
@@ -762,6 +796,8 @@ class Engine:
                     self._group_by(out, group_by, res)
                 elif order_by is not None and rc == 0:
                     self._order_by(out, order_by, res)
+                elif yield_by is not None and rc == 0:
+                    self._yield(out, yield_by, res, rows=rows)
                 if device_digest and rc == 0:
                     d3 = (c_u64 * 3)()
                     drc = self.L.ngx_go_result_digest(self.h, out, d3)
@@ -882,6 +918,46 @@ class Engine:
                     res.col_types = []
         finally:
             self.L.ngx_order_result_free(oout)
+
+    def go_yield(self, space: int, s: Union[str, ngql.GoSentence], spec: YieldSpec, pushdown: bool = True,
+                 now_sec: int = 0) -> GoResult:
+        """`s | YIELD ... [WHERE ...]`: the GO runs with its result left in HBM and the YIELD sentence filters,
+        projects or reduces it there (ngx_go_yield); only the kept rows' cells, or the one aggregate row, cross.
+        GoResult.rows / nrows / col_types are the sentence's (rows in the GO's row order), device_ms /
+        yield_device_ms its device time, kept_rows the rows WHERE kept, go_nrows / go_device_ms the traversal's.
+        NGX_E_UNSUPPORTED ("yield: ...") comes back as a result with that code and the reason: the caller runs
+        the host restatement (nebula_amd/yieldexec.py)."""
+        return self.go(space, s, pushdown=pushdown, now_sec=now_sec, yield_only=True, compact=True, yield_by=spec)
+
+    def _yield(self, go_out, spec: YieldSpec, res: GoResult, rows: bool = True):
+        names = (ctypes.c_char_p * max(1, len(spec.input_names)))(*[n.encode() for n in spec.input_names])
+        ys = (YieldColC * max(1, len(spec.yields)))()
+        for i, (fn, expr) in enumerate(spec.yields):
+            ys[i].fn, ys[i].expr, ys[i].expr_len = AGG_FN[fn], expr, len(expr)
+        where = spec.where or b""
+        plan = YieldPlanC(len(spec.input_names), names, where, len(where), len(spec.yields), ys)
+        yout = P(YieldResultC)()
+        rc = self.L.ngx_go_yield(self.h, go_out, ctypes.byref(plan), ctypes.byref(yout))
+        try:
+            res.go_device_ms, res.go_nrows = res.device_ms, res.nrows
+            if rc:
+                err = self.L.ngx_last_error(self.h).decode()
+                if rc != E_UNSUPPORTED:
+                    raise EngineError(rc, err)
+                res.ok, res.code, res.error = False, rc, err
+                return
+            y = yout.contents
+            strings = ctypes.string_at(y.strings, y.strings_len) if y.strings_len else b""
+            if rows:
+                res.rows = _cells(y.cells, y.nrows, y.ncols, strings)
+            else:                                                 # one copy of the cells, no Python tuples
+                raw = ctypes.string_at(ctypes.cast(y.cells, ctypes.c_void_p).value, y.nrows * y.ncols * 16) if y.nrows else b""
+                res.yield_cells = np.frombuffer(raw, dtype=[("kind", "<i4"), ("len", "<i4"), ("v", "<i8")]).reshape(y.nrows, y.ncols)
+            res.col_types = y.col_types[:y.ncols] if y.input_rows else []   # the first input row types them
+            res.nrows, res.kept_rows = y.nrows, y.kept_rows
+            res.device_ms = res.yield_device_ms = y.device_ms
+        finally:
+            self.L.ngx_yield_result_free(yout)
 
     def _group_order_by(self, go_out, group: GroupBySpec, order: OrderBySpec, res: GoResult):
         self._order_by(go_out, order, res, group=group)

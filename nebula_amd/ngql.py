@@ -648,6 +648,40 @@ def parse_group_by(src: str) -> GroupBySentence:
     return s
 
 
+# ------------------------------------------------------------------------------ YIELD sentence
+@dataclass
+class YieldSentence:
+    """Parsed `YIELD <yield_columns> [WHERE <expr>]` (yield_sentence, parser.yy:798-804). The grammar has no
+    DISTINCT here: `YIELD DISTINCT ...` is a syntax error."""
+    yields: List[AggCol] = field(default_factory=list)
+    where: Optional[Expr] = None
+
+    def column_names(self) -> List[str]:
+        """YieldExecutor::prepareYield (YieldExecutor.cpp:85-89): the alias, else expr->toString()."""
+        return [y.alias if y.alias else y.expr.to_string() for y in self.yields]
+
+
+def is_yield(src: str) -> bool:
+    return re.match(r"\s*YIELD\b", src, re.I) is not None
+
+
+def parse_yield(src: str) -> YieldSentence:
+    p = Parser(src)
+    p.expect("kw", "YIELD")
+    if p.is_kw("DISTINCT"):
+        raise SyntaxError("syntax error near `DISTINCT'")
+    s = YieldSentence()
+    s.yields = _agg_columns(p, "WHERE")
+    if not s.yields:
+        raise SyntaxError("syntax error near `YIELD'")
+    if p.i and p.toks[p.i - 1].kind == "op" and p.toks[p.i - 1].text == ",":
+        raise SyntaxError("syntax error near `,'")
+    if p.accept("kw", "WHERE"):
+        s.where = p.expression()
+    p.expect("eof")
+    return s
+
+
 # ------------------------------------------------------------------------------ ORDER BY / LIMIT sentences
 @dataclass
 class OrderBySentence:

@@ -36,8 +36,12 @@ library, include/nebula_gn.h ngx_go with input_* set):
     calls onResult_: its rows (VertexID | SrcVID, DstVID, Ranking, then the yields) feed the sentence piped behind
     it. The scan is the backend's (Engine.lookup, ngx_lookup): no host storage leg stands behind it, so a
     "lookup: ..." refusal is the sentence's error.
-GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only (the
-default keeps refusing them, as `| YIELD` is refused either way).
+  - YieldExecutor (src/graph/YieldExecutor.cpp): `... | YIELD <columns> [WHERE <expr>]` and `YIELD $var.x ...` over an
+    interim result (nebula_amd/yieldexec.py), when the caller opts in with yield_sentence=True. It calls onResult_:
+    its rows feed the sentence piped behind it. Behind a plain head GO the filter, the projection and the aggregates
+    run in the same device call where the backend has it (ngx_go_yield; Pipeline._go_yield).
+GO and GROUP BY are the traversal sentences here; ORDER BY and LIMIT run under order_limit=True only, and a YIELD
+sentence with an input under yield_sentence=True only (the default keeps refusing them).
 `backend` is an Engine (the product) or the oracle's Oracle: both take `go(space, s, input=...)`.
 """
 from __future__ import annotations
@@ -46,7 +50,7 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
 from . import fetch as fetchmod
-from . import findpath, groupby, ngql, orderby, setop
+from . import findpath, groupby, ngql, orderby, setop, yieldexec
 from . import lookup as lookupmod
 
 T_UNKNOWN, T_BOOL, T_INT, T_VID, T_FLOAT, T_DOUBLE, T_STRING, T_TIMESTAMP = 0, 1, 2, 3, 4, 5, 6, 21
@@ -169,8 +173,12 @@ class Pipeline:
                  order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
                  set_ops: bool = False, device_set_op: bool = True, find_path: bool = False,
                  device_find_path: bool = True, fetch: bool = False, device_fetch: bool = True, catalog=None,
-                 lookup: bool = False, indexes=None, **go_kw):
-        """lookup=True: LOOKUP ON sentences run (off by default, as the other opt-ins are); indexes are the space's
+                 lookup: bool = False, indexes=None, yield_sentence: bool = False, device_yield: bool = True, **go_kw):
+        """yield_sentence=True: YIELD sentences with a pipe input or a `$var` prop run (off by default, as the other
+        opt-ins are; the constant form runs either way); device_yield=False: every one takes the host restatement
+        (yieldexec.py) even where the backend could run it over the head GO's rows in HBM. yield_fallbacks counts
+        the device calls refused with "yield: ...", yield_refusal keeps the last refusal's text.
+        lookup=True: LOOKUP ON sentences run (off by default, as the other opt-ins are); indexes are the space's
         lookup.Index items (what the meta client's index cache holds); the schemas come from catalog, as for fetch.
         The backend has to have `lookup` (an Engine): the oracle has no index scan, and the Pipeline refuses to be
         built over it with lookup=True. lookups counts the sentences scanned, lookup_rows their rows.
@@ -193,6 +201,10 @@ class Pipeline:
         device_group_order=False: `GO | GROUP BY | [ORDER BY |] LIMIT` groups on the device and orders the group
         rows on the host, even where the backend could do both in one call (it takes all three switches on)."""
         self.device_group_order = device_group_order
+        self.yield_sentence = yield_sentence
+        self.device_yield = device_yield
+        self.yield_fallbacks = 0
+        self.yield_refusal = ""
         self.set_ops = set_ops
         self.device_set_op = device_set_op
         self.set_fallbacks = 0                                    # device set calls refused after both traversals ran
@@ -288,6 +300,78 @@ class Pipeline:
         p.expect("eof")
         types = [_KIND_TYPE[k] for k, _ in row]
         return Outcome(True, "", names, types, [tuple(row)])
+
+    def _yield(self, text: str, inp: Optional[Interim]) -> Outcome:
+        """A YIELD sentence over the pipe's input or a variable: YieldExecutor restated on the host (yieldexec.run)."""
+        try:
+            s = ngql.parse_yield(text)
+        except (SyntaxError, ValueError) as e:
+            return Outcome(False, "SyntaxError: %s" % e)
+        try:
+            if inp is None and not self._yield_reads(text):       # executeConstant's aggregate form
+                names, types, rows = yieldexec.run_constant(s)
+            else:
+                names, types, rows = yieldexec.run(s, inp, self.variables)
+        except yieldexec.YieldError as e:
+            return Outcome(False, str(e))
+        return Outcome(True, "", names, types, rows)
+
+    def _go_yield(self, go_text: str, yield_text: str) -> Optional[Outcome]:
+        """`GO | YIELD ... [WHERE ...]` with the sentence on the device (ngx_go_yield); None when the sentences run
+        one by one: a shape only the host words (a `$var`, an unknown column, a SyntaxError), or a "yield: ..."
+        refusal, which is counted and costs the traversal once more."""
+        from .engine import YieldSpec
+        g = self._plain_go(go_text)
+        if g is None:
+            return None
+        names = g.column_names(self.edge_names)
+        if len(set(names)) != len(names):
+            return None
+        try:
+            s = ngql.parse_yield(yield_text)
+            yields = yieldexec.expand(s, Interim(names), {})
+            yieldexec.check_agg(yields)
+            if yieldexec.syntax_check(s, yields) is not None:
+                return None
+        except (SyntaxError, ValueError, yieldexec.YieldError):
+            return None
+        props = [p for y in yields for p in y.expr.props()] + (s.where.props() if s.where is not None else [])
+        if any(prop not in names for _, _, prop in props):
+            return None
+        spec = YieldSpec(names, s.where.encode() if s.where is not None else None,
+                         [(y.fun, y.expr.encode()) for y in yields])
+        kw = {k: v for k, v in self.go_kw.items() if k in ("pushdown", "now_sec")}
+        try:
+            r = self.backend.go_yield(self.space, g, spec, **kw)
+        except RuntimeError as e:
+            if getattr(e, "code", 0) == -1002:                    # the device-resident GO itself: the plain path decides
+                return None
+            raise
+        if not r.ok:
+            if r.code == -1002 and r.error.startswith("yield:"):
+                self.yield_fallbacks += 1
+                self.yield_refusal = r.error
+            return None                                           # the GO's own error: the plain path words it
+        out_names = [y.alias if y.alias else y.expr.to_string() for y in yields]
+        return Outcome(True, "", out_names, list(r.col_types), list(r.rows))
+
+    @staticmethod
+    def _yield_reads(text: str) -> bool:
+        """Whether a YIELD sentence without pipe input is YieldExecutor's all the same: it names a prop (`$var.x` runs
+        over the variable, `$-.x` is its `Inputs nullptr.`, any other prop its syntaxCheck's error)."""
+        try:
+            s = ngql.parse_yield(text)
+            return bool([p for y in s.yields for p in y.expr.props()] + (s.where.props() if s.where is not None else []))
+        except (SyntaxError, ValueError):
+            return False
+
+    @staticmethod
+    def _yield_aggregates(text: str) -> bool:
+        """Whether a YIELD sentence carries a function (its constant form is YieldExecutor::AggregateConstant)."""
+        try:
+            return any(y.fun for y in ngql.parse_yield(text).yields)
+        except (SyntaxError, ValueError):
+            return False
 
     def _device_spec(self, go_text: str, gb_text: str):
         """(GoSentence, GroupBySentence, spec) when `GO | GROUP BY` can group on the device (ngx_go_group_by):
@@ -697,6 +781,14 @@ class Pipeline:
                         ngql.parse_lookup(body)
                     except (SyntaxError, ValueError) as e:
                         return Outcome(False, "SyntaxError: %s" % e)
+        if self.yield_sentence:
+            for part in parts:
+                body = _unwrap(part)
+                if len(_split(body, "|")) == 1 and ngql.is_yield(body):
+                    try:
+                        ngql.parse_yield(body)
+                    except (SyntaxError, ValueError) as e:
+                        return Outcome(False, "SyntaxError: %s" % e)
         cur = inp
         out = None
         skip = 0
@@ -708,6 +800,13 @@ class Pipeline:
                     cur = Interim.from_result(out.names, out.col_types, out.rows)
                 continue
             host_group = False
+            if self.yield_sentence and self.device_yield and getattr(self.backend, "device_yield", False) \
+                    and i + 1 < len(parts) and cur is None and body.upper().startswith("GO") \
+                    and ngql.is_yield(_unwrap(parts[i + 1])):
+                dev = self._go_yield(body, _unwrap(parts[i + 1]))
+                if dev is not None:
+                    out, skip = dev, 1
+                    continue
             if self.fetch and self.device_fetch and getattr(self.backend, "device_fetch", False) and i + 1 < len(parts) \
                     and cur is None and body.upper().startswith("GO") and ngql.is_fetch(_unwrap(parts[i + 1])):
                 dev = self._fetch(_unwrap(parts[i + 1]), None, go_text=body)
@@ -757,6 +856,9 @@ class Pipeline:
                 out = self._set(body, cur)                        # ( set_sentence ) as a traverse sentence
             elif len(_split(body, "|")) > 1:
                 out = self._piped(body, cur)                      # ( piped ) as a traverse sentence
+            elif self.yield_sentence and ngql.is_yield(body) and (cur is not None or self._yield_reads(body)
+                                                                  or self._yield_aggregates(body)):
+                out = self._yield(body, cur)
             elif body.upper().startswith("YIELD") and cur is None:
                 out = self._yield_constant(body)
             elif ngql.is_group_by(body):
@@ -808,8 +910,9 @@ def run(backend, space: int, text: str, edge_names: Sequence[str] = (), device_g
         order_limit: bool = False, device_order_by: bool = True, device_group_order: bool = True,
         set_ops: bool = False, device_set_op: bool = True, find_path: bool = False, device_find_path: bool = True,
         fetch: bool = False, device_fetch: bool = True, catalog=None, lookup: bool = False, indexes=None,
-        **go_kw) -> Outcome:
+        yield_sentence: bool = False, device_yield: bool = True, **go_kw) -> Outcome:
     return Pipeline(backend, space, edge_names, device_group_by=device_group_by, order_limit=order_limit,
                     device_order_by=device_order_by, device_group_order=device_group_order, set_ops=set_ops,
                     device_set_op=device_set_op, find_path=find_path, device_find_path=device_find_path, fetch=fetch,
-                    device_fetch=device_fetch, catalog=catalog, lookup=lookup, indexes=indexes, **go_kw).run(text)
+                    device_fetch=device_fetch, catalog=catalog, lookup=lookup, indexes=indexes,
+                    yield_sentence=yield_sentence, device_yield=device_yield, **go_kw).run(text)
